@@ -60,7 +60,19 @@ Multi-GPU work inside the JSON line (all timed, every rank, RCCL over xGMI):
   is the measured per-rank scan work after the exact cone pruning (the
   unpruned figure alongside).
 
-Usage: python bench.py [--gpus N --steps K --warmup W]. Without a torchrun
+A plain run does only what the headline figure needs: it loads the tenant,
+warms up, times the ``--steps`` steps and prints the result line (``value``,
+``ms_per_step`` and the run's configuration). Everything else described here
+-- recall against the float64 truth, the per-stage breakdown, the routed and
+global serving paths, the consolidation sections and the measured HBM peaks
+-- runs only under ``--full`` and adds its keys to the same line.
+``--dump-outputs DIR`` (either mode) writes what the last timed step returned
+to its caller: ``DIR/rows.npy``, the [batch, k] graph rows behind the step's
+``ResultBatch`` (float64; -1 = empty slot), rank r > 0 as ``rows.rank<r>.npy``.
+The inputs are seeded, so two builds can be compared output for output.
+
+Usage: python bench.py [--gpus N --steps K --warmup W] [--full]
+[--dump-outputs DIR]. Without a torchrun
 environment the script launches N ranks itself through torch.distributed.run
 (127.0.0.1 rendezvous) before touching any GPU -- N = 1 included, so every
 serving path runs its collectives on RCCL -- and exits with their status
@@ -165,6 +177,24 @@ def recall_misses(g, Q, found_rows, truth_s, truth_rows, limit: int = 8):
     return out
 
 
+def dump_outputs(out_dir: str, res, k: int, rank: int) -> None:
+    """``--dump-outputs``: what the last timed step handed to its caller, as
+    one [batch, k] float64 array of graph rows (query q's nodes in rank order,
+    -1 = empty slot; a row index is exact in float64)."""
+    import numpy as np
+    if res is None:
+        raise SystemExit("bench.py: --dump-outputs needs at least one timed step")
+    rows = getattr(res, "rows", None)
+    if rows is None:  # a plain list of node lists (the store does not bind the graph)
+        rows = np.full((len(res), k), -1, dtype=np.int64)
+        for q, nodes in enumerate(res):
+            r = [n._r for n in nodes][:k]
+            rows[q, :len(r)] = r
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "rows.npy" if rank == 0 else f"rows.rank{rank}.npy"),
+            np.asarray(rows, dtype=np.float64))
+
+
 def _free_port() -> int:
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
@@ -249,6 +279,13 @@ def main():
     ap.add_argument("--max-len", type=int, default=64)
     ap.add_argument("--recall-queries", type=int, default=1024)
     ap.add_argument("--json-out", default="")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run the recall check, the per-stage breakdown, the routed / global "
+                         "serving paths and the consolidation sections (the options for those sections only apply "
+                         "here); off by default: a plain run times the headline steps and prints the result line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the last timed step's results (the [batch, k] rows of its ResultBatch, float64) to "
+                         "DIR/rows.npy after the timed steps")
     ap.add_argument("--prewarm-s", type=float, default=3.0, help="untimed GPU clock ramp before the warmup steps")
     ap.add_argument("--consolidate-steps", type=int, default=10,
                     help="second half of the metric: timed consolidation steps on a --rows-node buffer (0 = skip)")
@@ -446,6 +483,49 @@ def main():
             print(json.dumps({"ms_per_step": round(el / a.steps * 1e3, 3), "steps": a.steps, "qps": round(qps, 2)}),
                   flush=True)
         return
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, res, a.k, rank)
+    S_tok = int(emb.tok.encode_batch(pool[0], emb.max_len)[0].shape[1])
+    head = {
+        "metric": METRIC,
+        "value": round(qps, 2),
+        "unit": "queries/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": round(el / a.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16 encoder; int8 scan -> bf16 re-score -> fp32 re-rank",
+        "data": "synthetic (random unit fp32 memory vectors, synthetic query texts, random-init encoder weights)",
+        "config": {"model": "%s (d=%d) on-device embed + MemorySystem.search_memories top-%d over a "
+                            "%d x %d fp32 tenant per GPU (L2, fp32 re-rank)"
+                            % ({"bge-base": "bge-base-en"}.get(a.model, a.model), a.dim, a.k, a.rows, a.dim),
+                   "global_batch": world * a.batch, "seq_len": S_tok, "parallelism": "tenant-dp%d" % world},
+        "path": "DistributedMemoryService -> owner's MemorySystem.search_memories_stream (pipelined "
+                "search_memories_batch); tenants placed by rendezvous hashing, one per GPU",
+        "full": bool(a.full),
+        "load_s": round(t_load, 1),
+        "gc_in_timed_loop": {"startup_heap_frozen": bool(a.gc_freeze),
+                             **{f"gen{k}": {"passes": v[0], "ms": round(v[1] * 1e3, 2)} for k, v in gc_log.items()}},
+        "prewarm_s": round(t_pre, 1),
+    }
+
+    def finish(out):
+        if rank == 0:
+            line = json.dumps(out)
+            print(line, flush=True)
+            if a.json_out:
+                with open(a.json_out, "w") as f:
+                    f.write(line + "\n")
+        if distributed:
+            dist.barrier(group=hg)
+            dist.destroy_process_group()
+    if not a.full:
+        svc.close()
+        finish(head)
+        return
 
     # ---- timed: routed search (every front end's queries spread over ALL
     # ranks' tenants: all-to-all there and back) and global search (each
@@ -574,7 +654,6 @@ def main():
     ts_r, truth_r = exact_l2_topk(g, Qr, a.k)
     rec_rand = recall(rows_r.cpu().tolist(), truth_r)
     miss_r = recall_misses(g, Qr, rows_r.cpu().tolist(), ts_r, truth_r) if rec_rand < 1.0 else []
-    S_tok = int(emb.tok.encode_batch(pool[0], emb.max_len)[0].shape[1])
     lens = emb.tok.encode_batch(pool[0], emb.max_len)[1]
 
     # measured per-rank HBM peak of each section, next to hbm_plan's estimate,
@@ -665,24 +744,7 @@ def main():
                                  dim=a.dim, clustered=True, prune_threshold=0.0)
         peak("consolidate_sharded_persistent_graph")
     res = {
-        "metric": METRIC,
-        "value": round(qps, 2),
-        "unit": "queries/s",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": round(el / a.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "bf16 encoder; int8 scan -> bf16 re-score -> fp32 re-rank",
-        "data": "synthetic (random unit fp32 memory vectors, synthetic query texts, random-init encoder weights)",
-        "config": {"model": "%s (d=%d) on-device embed + MemorySystem.search_memories top-%d over a "
-                            "%d x %d fp32 tenant per GPU (L2, fp32 re-rank)"
-                            % ({"bge-base": "bge-base-en"}.get(a.model, a.model), a.dim, a.k, a.rows, a.dim),
-                   "global_batch": world * a.batch, "seq_len": S_tok, "parallelism": "tenant-dp%d" % world},
-        "path": "DistributedMemoryService -> owner's MemorySystem.search_memories_stream (pipelined "
-                "search_memories_batch); tenants placed by rendezvous hashing, one per GPU",
+        **head,
         "serving": serving,
         "recall_at_10": round(rec_api, 4),
         "recall_at_10_random_queries": round(rec_rand, 4),
@@ -699,10 +761,6 @@ def main():
                              "cut -> fp32 re-rank; recall checked against float64 truth" if t_lowp is not None else
                              "bf16 MFMA candidate scan -> fp32 re-rank; recall checked against float64 truth"),
         "tokens_per_query": {"padded": S_tok, "real_mean": round(float(lens.float().mean()), 2)},
-        "load_s": round(t_load, 1),
-        "gc_in_timed_loop": {"startup_heap_frozen": bool(a.gc_freeze),
-                             **{f"gen{k}": {"passes": v[0], "ms": round(v[1] * 1e3, 2)} for k, v in gc_log.items()}},
-        "prewarm_s": round(t_pre, 1),
         "hbm_per_rank": {"peak_gib_measured": hbm_peak, "allocated_gib_at_section_start": hbm_start,
                          "plan": hbm_plan(a.rows, a.dim, a.batch, a.consolidate_convs, world=a.gpus)},
     }
@@ -739,15 +797,7 @@ def main():
     from lazzaro_amd.ops import search as _S
     if _S.SPEC_STATS:  # LZK_SPEC_STATS=1 (diagnostic): queries sent to the exact fallback per store search
         res["spec_fallback_queries"] = [int(x) for x in _S.SPEC_STATS[:64]]
-    if rank == 0:
-        line = json.dumps(res)
-        print(line, flush=True)
-        if a.json_out:
-            with open(a.json_out, "w") as f:
-                f.write(line + "\n")
-    if distributed:
-        dist.barrier(group=hg)
-        dist.destroy_process_group()
+    finish(res)
 
 
 if __name__ == "__main__":

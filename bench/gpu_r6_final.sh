@@ -8,7 +8,7 @@ export PYTHONPATH=$PWD${PYTHONPATH:+:$PYTHONPATH}
 OUT=${OUT:-gpurun_out/r6fin}
 mkdir -p $OUT
 if [ -z "$NOBENCH" ]; then
-  timeout -k 10 700 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || exit 1
+  timeout -k 10 700 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err || exit 1
 fi
 for cfg in default persistent; do
   A=""; [ $cfg = persistent ] && A="--prune-threshold 0"

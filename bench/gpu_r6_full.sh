@@ -9,5 +9,5 @@ if [ -z "$NOTEST" ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || exit 1
 fi
 if [ -z "$NOBENCH" ]; then
-  timeout -k 10 700 python bench.py --gpus 1 --steps 20 --warmup 5 ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err || exit 1
+  timeout -k 10 700 python bench.py --gpus 1 --steps 20 --warmup 5 --full ${BENCH_ARGS} > $OUT/bench.json 2> $OUT/bench.err || exit 1
 fi

@@ -21,7 +21,7 @@ def _port():
 def test_bench_two_ranks_cpu(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
-           "--cpu", "--gpus", "2", "--rows", "6000", "--dim", "128", "--model", "tiny", "--batch", "32",
+           "--cpu", "--full", "--gpus", "2", "--rows", "6000", "--dim", "128", "--model", "tiny", "--batch", "32",
            "--steps", "2", "--warmup", "1", "--prewarm-s", "0.2", "--recall-queries", "8", "--consolidate-steps", "1",
            "--consolidate-convs", "4", "--sharded-persistent-steps", "0"]
     env = dict(os.environ, PYTHONPATH=ROOT, LZK_BENCH_DB=str(tmp_path / "db"))
@@ -44,7 +44,7 @@ def _check_serving(d, batch):
     assert 0 < sv["routed_remote_frac_rank0"] < 1
 
 
-SMALL = ["--cpu", "--rows", "6000", "--dim", "128", "--model", "tiny", "--batch", "32", "--steps", "2", "--warmup",
+SMALL = ["--cpu", "--full", "--rows", "6000", "--dim", "128", "--model", "tiny", "--batch", "32", "--steps", "2", "--warmup",
          "1", "--prewarm-s", "0.2", "--recall-queries", "8", "--consolidate-steps", "1", "--consolidate-convs", "4",
          "--no-persistent-graph", "--sharded-steps", "1", "--global-batch", "8", "--sharded-persistent-steps", "0"]
 
@@ -67,6 +67,39 @@ def test_bench_self_launches_ranks(tmp_path):
     assert d["consolidate_sharded"]["turns_per_s"] > 0
 
 
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """Without ``--full`` the bench times the headline steps and stops: the
+    result line carries the headline keys and none of the other sections.
+    ``--dump-outputs`` writes the last timed step's [batch, k] rows (float64),
+    the same from run to run."""
+    import numpy as np
+    plain = [a for a in SMALL if a != "--full"]
+    outs = []
+    for name in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dump-outputs",
+               str(tmp_path / name)] + plain
+        env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR",
+                                                                "MASTER_PORT", "TORCHELASTIC_RUN_ID")}
+        env.update(PYTHONPATH=ROOT, LZK_BENCH_DB=str(tmp_path / ("db" + name)))
+        r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+        assert d["unit"] == "queries/s" and d["higher_is_better"] is True and d["dtype"] and d["metric"]
+        assert d["full"] is False
+        assert not {"serving", "recall_at_10", "breakdown_ms", "consolidate", "consolidate_sharded",
+                    "hbm_per_rank"} & set(d)
+        assert sorted(os.listdir(tmp_path / name)) == ["rows.npy"]
+        outs.append(np.load(tmp_path / name / "rows.npy"))
+    a, b = outs
+    assert a.dtype == np.float64 and a.shape == (32, 10)
+    assert (a >= 0).all() and (a < 6000).all() and (a == np.floor(a)).all()
+    assert all(len(set(row)) == 10 for row in a.tolist())  # ten distinct nodes per query
+    assert np.array_equal(a, b)
+
+
 def test_bench_rejects_gpus_world_mismatch(tmp_path):
     env = dict(os.environ, PYTHONPATH=ROOT, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + SMALL, cwd=str(tmp_path),
@@ -85,7 +118,7 @@ def test_bench_eight_ranks_cpu(tmp_path):
            "--gpus", "8", "--rows", "5000", "--dim", "128", "--model", "tiny", "--batch", "16", "--steps", "1",
            "--warmup", "1", "--prewarm-s", "0", "--recall-queries", "4", "--consolidate-steps", "1",
            "--consolidate-convs", "2", "--no-persistent-graph", "--sharded-steps", "1", "--global-batch", "4",
-           "--sharded-persistent-steps", "1", "--cpu"]
+           "--sharded-persistent-steps", "1", "--cpu", "--full"]
     env = dict(os.environ, PYTHONPATH=ROOT, LZK_BENCH_DB=str(tmp_path / "db"), OMP_NUM_THREADS="1")
     r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
