@@ -83,14 +83,15 @@ def _unit(x):
 
 def build_tenant(dev, nodes: int, dim: int, encoder, seed: int, db_dir: str, cluster_convs: int, n_fine: int,
                  n_top: int, cluster_iters: int, init_edges: int, prune_threshold: float = 0.5,
-                 persist_async: bool = False):
+                 persist_async: bool = False, compact_dead_fraction=None):
     from bench import populate  # the headline bench's tenant loader
     from lazzaro_amd.core.memory_system import MemorySystem
     from lazzaro_amd.core.providers import HashEmbedder, LocalLLM
 
     ms = MemorySystem(llm_provider=LocalLLM(), embedding_provider=encoder or HashEmbedder(dim=dim), device=dev,
                       db_dir=db_dir, load_from_disk=False, enable_async=False, max_buffer_size=nodes,
-                      prune_threshold=prune_threshold, persist_async=persist_async, hierarchy_mode="kmeans", hierarchy_params={"fine": n_fine, "top": n_top,
+                      prune_threshold=prune_threshold, persist_async=persist_async,
+                      compact_dead_fraction=compact_dead_fraction, hierarchy_mode="kmeans", hierarchy_params={"fine": n_fine, "top": n_top,
                                                                  "every": cluster_convs, "iters": cluster_iters})
     g = ms.graph
     g._set_dim(dim)
@@ -136,15 +137,16 @@ def _sync(dev):
 def run(comm, dev, nodes: int, convs: int, facts: int, steps: int, warmup: int, encoder=None, dim: int = 768,
         dup_rate: float = 0.1, seed: int = 7, cluster_every: int = 5, n_fine: int = 4096, n_top: int = 64,
         cluster_iters: int = 2, init_edges: int = None, db_dir: str = None, prune_threshold: float = 0.5,
-        persist_async: bool = False, stream: bool = True, lookahead: int = 2):
-    """``stream``: the batches go through ``MemorySystem.consolidate_stream``
+        persist_async: bool = False, stream: bool = True, lookahead: int = 2, compact_dead_fraction=None):
+    """``compact_dead_fraction``: MemorySystem's row reclamation knob (the
+    result then reports rows / capacity / compactions). ``stream``: the batches go through ``MemorySystem.consolidate_stream``
     (batch i+1's candidate scan under batch i's apply; results identical to
     the per-batch calls, tests/kernels/test_tenant_engine_gpu.py); False:
     one ``consolidate_batch`` call per step."""
     db_dir = db_dir or tempfile.mkdtemp(prefix=f"lzcons{comm.rank}_")
     init_edges = 2 * nodes if init_edges is None else init_edges
     ms = build_tenant(dev, nodes, dim, encoder, seed + 31 * comm.rank, db_dir, cluster_every * convs, n_fine, n_top,
-                      cluster_iters, init_edges, prune_threshold, persist_async)
+                      cluster_iters, init_edges, prune_threshold, persist_async, compact_dead_fraction)
     edges_start = ms.graph.num_edges
     gen = torch.Generator(device=dev).manual_seed(seed + 100 + comm.rank)
     rng = random.Random(seed + comm.rank)
@@ -246,6 +248,8 @@ def run(comm, dev, nodes: int, convs: int, facts: int, steps: int, warmup: int, 
                                        "iters_per_pass": cluster_iters, "seed_pass_ms": round(seed_ms, 1),
                                        "farthest_first_ms": ff.get("ms")},
            "stages_ms": stages,
+           "rows_rank0": g.n, "capacity_rank0": g.cap, "compact_dead_fraction": compact_dead_fraction,
+           "row_epoch_rank0": g.row_epoch, "rows_reclaimed_rank0": g.rows_reclaimed_total,
            "persistence": "incremental columnar commit per step (db on local disk)" + (
                ", write-behind (persist_async: commits on a writer thread, flushed inside the timed region)"
                if persist_async else "")}
@@ -457,6 +461,8 @@ if __name__ == "__main__":
                     help="native applier: a node-salience pass per segment instead of the lazy stamps (A/B)")
     ap.add_argument("--lookahead", type=int, default=2,
                     help="consolidate_stream: batches drawn ahead (1 = the next one only; A/B)")
+    ap.add_argument("--compact-dead-fraction", type=float, default=None,
+                    help="MemorySystem(compact_dead_fraction=): reclaim dead rows after a commit (default: never)")
     ap.add_argument("--cluster-inline", action="store_true",
                     help="k-means passes in line instead of in the background (A/B)")
     a = ap.parse_args()
@@ -485,7 +491,7 @@ if __name__ == "__main__":
              **({"clustered": a.clustered, "cadence": a.cadence, "stream": a.stream,
                  "prune_threshold": a.prune_threshold} if a.sharded else
                 {"prune_threshold": a.prune_threshold, "persist_async": a.persist_async, "stream": a.stream,
-                 "lookahead": a.lookahead}))
+                 "lookahead": a.lookahead, "compact_dead_fraction": a.compact_dead_fraction}))
     if comm.rank == 0:
         print(json.dumps({"metric": "consolidate turns/sec", "n_gpus": comm.world, **res}), flush=True)
     if comm.enabled:

@@ -325,6 +325,7 @@ class ConsolidationMixin:
             self.short_term_memory = []
             self.conversation_history = []
             self._save_to_persistence()
+            self._maybe_compact()
         return "\n".join(results)
 
     def _fact_shard_key(self, f: Dict) -> str:
@@ -760,6 +761,8 @@ class ConsolidationMixin:
             if self.query_cache:
                 self.query_cache.invalidate_results()
             self._save_to_persistence()
+            # (in a stream, the next batch's prefetched scan is invalidated through the row epoch)
+            self._maybe_compact()
         return stats
 
     def consolidate_stream(self, batches, cadence: str = "conversation", commit: str = "batch",

@@ -125,6 +125,7 @@ class MemorySystem(ConsolidationMixin):
         hierarchy_mode: str = "reference",
         hierarchy_params: Optional[Dict] = None,
         persist_async: bool = False,
+        compact_dead_fraction: Optional[float] = None,
     ):
         self.model = model
         self.user_id = user_id
@@ -191,6 +192,14 @@ class MemorySystem(ConsolidationMixin):
         self._writes: List = []
         self._unwritten: List = []  # snapshots whose commit failed, retried first
         self._wb_lock = threading.Lock()
+        # row reclamation (opt-in, compact_memory): None = never on its own;
+        # a fraction f = after a commit, once at least f of the tenant's rows
+        # are not nodes (evicted / pruned ghosts), reclaim them
+        if compact_dead_fraction is not None and not 0.0 < float(compact_dead_fraction) <= 1.0:
+            raise ValueError("compact_dead_fraction must be in (0, 1] or None")
+        self.compact_dead_fraction = None if compact_dead_fraction is None else float(compact_dead_fraction)
+        self._compact_tried_n = 0  # rows at the last attempt that reclaimed nothing
+        self._compact_kept = 0  # dead rows the last compaction had to keep (still referenced)
 
         self.query_cache = QueryCache(max_size=1000) if enable_caching else None
         self.consolidation_queue: List[Dict] = []
@@ -273,6 +282,7 @@ class MemorySystem(ConsolidationMixin):
         if detach is not None:
             detach(self.user_id)
         self.graph = self._new_graph()
+        self._compact_tried_n = self._compact_kept = 0
 
     # ------------------------------------------------------------ helpers
     def _say(self, msg: str) -> None:
@@ -671,13 +681,13 @@ class MemorySystem(ConsolidationMixin):
                         # ~16 MB/s in the serving loop: 5-7 ms per 1024 x 10 batch)
                         ev = torch.cuda.Event(blocking=BLOCKING_EVENTS)
                         ev.record()
-                        return ("rows_dev", g, rows, ev)
-                    return ("rows", g, rows, None)
+                        return ("rows_dev", g, rows, ev, g.row_epoch)
+                    return ("rows", g, rows, None, g.row_epoch)
         with tracer.stage("search", self._device):
-            return ("ids", None, self._search_batch(embs, limit), None)
+            return ("ids", None, self._search_batch(embs, limit), None, 0)
 
     def _search_finish(self, h) -> List[List[Node]]:
-        kind_, g0, data, ev = h
+        kind_, g0, data, ev, epoch = h  # (the row epoch searched under: a compaction may run before the finish)
         if kind_ == "rows_dev":
             st = getattr(self, "_result_stream", None)
             if st is None:
@@ -692,9 +702,10 @@ class MemorySystem(ConsolidationMixin):
             g = self.graph
             if kind_ == "rows" and g is g0:  # non-node rows were set to -1 on the device
                 # lazy per-row views: no Python object per result row until read
-                return ResultBatch(g, data.numpy() if not data.is_cuda else data.cpu().numpy())
+                return ResultBatch(g, data.numpy() if not data.is_cuda else data.cpu().numpy(), epoch)
             if kind_ == "rows":  # the tenant was switched while the search ran
-                data = [[g0.ids[r] for r in row if r >= 0] for row in data.tolist()]
+                data = [[g0.ids[r] for r in row if r >= 0]
+                        for row in g0.translate_rows(data.numpy(), epoch).tolist()]
             out = []
             for ids in data:
                 rows = [r for r in (g.row_of.get(i, -1) for i in ids) if r >= 0]
@@ -744,7 +755,8 @@ class MemorySystem(ConsolidationMixin):
         g, m = self.graph, self.metrics
         sq, sms = m.get("search_queries", 0), m.get("search_ms", 0.0)
         return {"device": str(self._device), "graph_rows": g.n, "hbm_graph_bytes": self._graph_bytes(),
-                "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
+                "dead_rows": g.n - g.num_nodes(), "row_epoch": g.row_epoch,
+                "rows_reclaimed_total": g.rows_reclaimed_total, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
                 "avg_search_batch_ms": round(sms / m["search_batches"], 3) if m.get("search_batches") else 0.0}
 
     def _graph_bytes(self) -> int:
@@ -1008,6 +1020,50 @@ STORAGE:
             self._writer.submit(self._write_job, args, prof).result()
             if self._unwritten and self.strict_errors:
                 raise StoreError(f"write-behind commit failed for {self.user_id}")
+
+    # ------------------------------------------------------------ row reclamation
+    def compact_memory(self, shrink: bool = False) -> Dict:
+        """Reclaim the tenant's dead rows (:meth:`TenantGraph.compact`): the
+        rows of evicted and pruned nodes that no edge, parent or store row
+        still refers to leave the HBM columns, the others slide down in
+        order. Nothing a caller can observe by id changes; every row-bound
+        scan gets shorter. Pending persistence is flushed first (committed
+        rows are clean, deletions are in the store), the retrieval cache is
+        dropped as after any commit. ``shrink``: also give capacity back.
+        Returns the engine's counts plus ``ms``. A store with an IVF-PQ index
+        rebuilds it on the next search."""
+        t0 = time.perf_counter()
+        with self._graph_lock:
+            self.flush_persistence()
+            if self._persist_pending:
+                self._save_to_persistence()
+            with tracer.stage("compact", self._device):
+                out = self.graph.compact(shrink=shrink)
+            if self.query_cache:
+                self.query_cache.invalidate_results()
+        out["ms"] = (time.perf_counter() - t0) * 1e3
+        return out
+
+    def _maybe_compact(self) -> None:
+        """The ``compact_dead_fraction`` check after a commit, from host
+        counters only: enough rows are not nodes, and the tenant has grown
+        since the last attempt that reclaimed nothing. Ghosts that edges keep
+        alive must not trigger a compaction every step, so the rows the last
+        compaction had to keep do not count: the dead rows that have appeared
+        since must reach the fraction."""
+        f = self.compact_dead_fraction
+        if f is None:
+            return
+        g = self.graph
+        dead = g.n - g.num_nodes()
+        if g.n == 0 or g.n <= self._compact_tried_n or dead - self._compact_kept < f * g.n:
+            return
+        if g._seg_open or g._cc is not None:  # (a batch that failed mid-segment: not now)
+            return
+        out = self.compact_memory()
+        g = self.graph
+        self._compact_kept = g.n - g.num_nodes()
+        self._compact_tried_n = g.n if out["reclaimed"] == 0 else 0
 
     def _persist_failed(self, e) -> None:
         self.metrics["persist_failures"] = self.metrics.get("persist_failures", 0) + 1

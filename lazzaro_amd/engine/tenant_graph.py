@@ -24,7 +24,10 @@ store vector search     vector_store.py:132-140                     fused MFMA t
                                                                     fp32 re-rank
 =====================  ==========================================  =====================
 
-Node columns (row-indexed; rows are never reused while referenced):
+Node columns (row-indexed; a row keeps its index until :meth:`TenantGraph.compact`
+-- opt-in -- reclaims the rows nothing refers to any more and slides the rest
+down in their order; ``row_epoch`` / ``translate_rows`` serve whoever holds
+rows across one):
 
 * ``emb32`` fp32 [cap, D]: exact vectors (the store's precision, reference
   ``vector_store.py:37``); ``emb16`` bf16 [cap, Dp] on the GPU: the operand of
@@ -150,6 +153,10 @@ RERANK64_KERNEL = True
 # queries rounded to bf16 (relative 2^-9 each) move a cosine by at most
 # 2^-8 * sum|q_i x_i| <= 2^-8 ~ 0.0039, plus fp32 accumulation order.
 COS_FLOOR_SLACK = 0.01
+# TenantGraph.compact on the GPU through compact.hip (in place, one bounce
+# buffer); COMPACT_KERNEL = False: the torch formulation the CPU runs
+# (col[:m] = col[keep_idx], a second copy of each column's kept rows)
+COMPACT_KERNEL = True
 
 
 def _str_column(items=None):
@@ -349,6 +356,12 @@ class TenantGraph:
         # inside a consolidation batch cost no host synchronisation
         self._drop_pending: List[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = []
         self.last_add_rows: Sequence[int] = range(0)
+        # row reclamation (compact): the epoch counts the compactions that
+        # moved rows; _reclaimed[e] = the sorted old rows epoch e -> e + 1 dropped
+        self.row_epoch = 0
+        self._reclaimed: List[np.ndarray] = []
+        self.rows_reclaimed_total = 0
+        self._seg_open = False  # between segment_begin and segment_end
         self._norm_dev_pending: List[torch.Tensor] = []
         self.track = True
         self.stream = _side_stream(self.device) if self.on_gpu else None
@@ -1443,6 +1456,7 @@ class TenantGraph:
         :meth:`decay` followed by :meth:`remove_nodes` in segment_end."""
         if prune_threshold is not None and prune_threshold <= 0.0:
             prune_threshold = None
+        self._seg_open = True
         if not self.on_gpu:
             return {"pruned": self.decay(rate, prune_threshold, steps=steps)}
         tok = {"flag": None, "ne0": self.num_edges}
@@ -1463,6 +1477,7 @@ class TenantGraph:
         edges and remove the ``victims`` rows like :meth:`remove_nodes`
         (ghost rows, their shard's incident edges gone). Returns #pruned."""
         vic = victims.tolist() if torch.is_tensor(victims) else list(victims)
+        self._seg_open = False
         if "pruned" in tok:
             if vic:
                 self.remove_nodes(vic, drop_edges=True, unstore=unstore)
@@ -2240,7 +2255,7 @@ class TenantGraph:
                 t.record_stream(cur)
                 t.record_stream(stream)
         return {"n": self.n, "ra": ra, "rb": rb, "ev": ev, "Qn": Qn, "Q": Q, "ql": dual_label.to(dev, torch.int32),
-                "min_score": min_score, "keep": keep}
+                "min_score": min_score, "keep": keep, "epoch": self.row_epoch}
 
     def cos_topk_finish(self, h: Dict, k: int, mask: torch.Tensor):
         """(list A, list B) of a prefetched dual scan against the graph NOW
@@ -2257,6 +2272,12 @@ class TenantGraph:
             with tracer.stage("cb_prefetch_wait", "cpu"):
                 h["ev"].synchronize()
         torch.cuda.current_stream(dev).wait_event(h["ev"])
+        if h.get("epoch", self.row_epoch) != self.row_epoch:
+            # rows moved under the handle (compact): its lists name old rows --
+            # discard them and scan the graph as it is now
+            out = self._cos_topk(h["Q"], k, mask, h["ql"], h["min_score"])
+            h.clear()
+            return out
         n0, n = h["n"], self.n
         Qn, ra, rb, ql = h["Qn"], h["ra"], h["rb"], h["ql"]
         parts = [[self._rerank_cos(Qn, ra, k)], [self._rerank_cos(Qn, rb, k)]]
@@ -2781,6 +2802,194 @@ class TenantGraph:
             if not bool(has.any()):
                 return None
             return self.emb32[rows[has]].double().mean(0)
+
+    # ------------------------------------------------------------------ row reclamation
+    def _big_columns(self) -> List[torch.Tensor]:
+        return [t for t in (self.emb32, self.emb16, self.emb8) if t is not None]
+
+    def _narrow_columns(self) -> List[Tuple[torch.Tensor, float]]:
+        """(column, fill value) of every per-row column narrower than a vector."""
+        cols = [(t, 0) for t in (self.sqn, self.rs8) if t is not None]
+        cols += [(getattr(self, name), fill) for name, _, fill in self.NODE_COLS]
+        st = getattr(self, "_dstamp", None)
+        if st is not None and st.numel() >= self.n:
+            cols.append((st, 0))
+        return cols
+
+    @staticmethod
+    def _translate_once(rows: np.ndarray, dead: np.ndarray) -> np.ndarray:
+        """Rows of one epoch in the next: old - #reclaimed rows below it; -1
+        for a reclaimed (or already absent) row."""
+        pos = np.searchsorted(dead, rows)
+        gone = rows < 0
+        if dead.size:
+            gone |= dead[np.minimum(pos, dead.size - 1)] == rows
+        return np.where(gone, -1, rows - pos)
+
+    def translate_rows(self, rows, epoch: int) -> np.ndarray:
+        """``rows`` (any int array shape) as read under ``row_epoch == epoch``,
+        in today's numbering: the remaps of every compaction since composed;
+        -1 for a row that was reclaimed (and for -1). A holder of rows outside
+        the graph records ``row_epoch`` with them and reads them through this."""
+        a = np.asarray(rows, dtype=np.int64)
+        if not 0 <= epoch <= self.row_epoch:
+            raise ValueError(f"epoch {epoch} outside [0, {self.row_epoch}]")
+        for e in range(epoch, self.row_epoch):
+            a = self._translate_once(a, self._reclaimed[e])
+        return a
+
+    def compact(self, shrink: bool = False, chunk_rows: Optional[int] = None) -> Dict:
+        """Reclaim the rows nothing refers to any more, in place and stably:
+        the surviving rows slide down and keep their relative order, so every
+        tie-break by row -- similarity, importance, first rows, digests --
+        stays what it was, and the graph is, by id, the graph that was never
+        compacted. (One visible difference: a reclaimed id added again takes a
+        fresh row at the end, like a key deleted from and re-inserted into the
+        reference's dict.)
+
+        A row goes iff it is not a node, not a store row, not dirty, no edge's
+        endpoint and no kept row's parent. Ghosts that are still referenced
+        stay. The error-model accumulators (``sumsq``, ``n_sumsq``,
+        ``_rs8_max``, ``_max_norm_dev``) are sums / maxima over rows ever
+        written and stay valid bounds, untouched.
+
+        On the GPU the wide columns move in place chunk by chunk
+        (compact.hip; ``chunk_rows`` rows per chunk, one bounce buffer of
+        chunk_rows x row bytes, by default at most ops.tenant_ops
+        RC_BOUNCE_BYTES); COMPACT_KERNEL = False and the CPU take the torch
+        formulation. ``shrink``: then re-allocate to max(initial capacity,
+        ceil(1.1 n)) rows. The IVF-PQ index of a large store, keyed by row,
+        is rebuilt on its next use. Not while a segment or an incremental
+        components window is open. Holders of rows: see :meth:`translate_rows`.
+
+        Returns rows_before, rows_after, reclaimed, ghosts_kept, capacity,
+        bytes_moved, epoch."""
+        from ..utils.tracing import tracer
+        if self._cc is not None or self._seg_open:
+            raise RuntimeError("compact() inside an open consolidation segment / components window")
+        self.cluster_join()
+        _ = self.deleted_edges  # pending device rows -> ids, while rows still name them
+        n = self.n
+        out = {"rows_before": n, "rows_after": n, "reclaimed": 0, "ghosts_kept": 0, "capacity": self.cap,
+               "bytes_moved": 0, "epoch": self.row_epoch}
+        if n == 0:
+            return out
+        dev = self.device
+        kernel = self.on_gpu and COMPACT_KERNEL
+        with self.on_stream():
+            esrc, edst = self.e["src"], self.e["dst"]
+            keep = (T.rc_mark if kernel else T.rc_mark_ref)(self.kind[:n], self.stored[:n], self.dirty[:n],
+                                                            self.parent[:n], esrc, edst)
+            remap = T.rc_remap_of(keep)
+            dead_t = torch.nonzero(keep == 0).flatten()
+            head = torch.stack([remap[n].long(), ((self.kind[:n] != NODE) & (keep != 0)).sum(),
+                                dead_t[0] if dead_t.numel() else torch.zeros((), dtype=torch.long, device=dev)])
+            m, ghosts, first = (int(x) for x in head.cpu().tolist())
+            out["ghosts_kept"] = ghosts
+            if m == n:
+                return out
+            dead = dead_t.cpu().numpy().astype(np.int32 if n < (1 << 31) else np.int64)
+            keep_h = torch.nonzero(keep).flatten().cpu().numpy()
+            # views of rows about to go: their last field values, read while the rows still hold them
+            views = self.__dict__.get("_node_views") or {}
+            detach = {}
+            if views:
+                vr = np.fromiter(views.keys(), dtype=np.int64, count=len(views))
+                new_vr = self._translate_once(vr, dead)
+                for r, nr in zip(vr.tolist(), new_vr.tolist()):
+                    if nr < 0:
+                        v = views[r]
+                        detach[r] = {f: getattr(v, f) for f in (
+                            "id", "content", "embedding", "type", "timestamp", "access_count", "last_accessed",
+                            "salience", "is_super_node", "child_ids", "parent_id", "shard_key")}
+            # ---- device columns
+            big, narrow = self._big_columns(), self._narrow_columns()
+            moved = 0
+            with tracer.stage("compact_move", dev):  # (device time of the moves under LZK_TRACE=1)
+                if kernel:
+                    rb = max((t.shape[1] * t.element_size() for t in big), default=4)
+                    ch = int(chunk_rows) if chunk_rows else T.rc_chunk_rows(rb)
+                    bounds = T.rc_bounds(remap, n, first, ch)
+                    bounce = torch.empty(min(ch, n - first) * rb, dtype=torch.uint8, device=dev) if big else None
+                    for t in big:
+                        moved += T.rc_move_rows(t, keep, remap, n, first, ch, bounds, bounce)[0]
+                    del bounce
+                    T.rc_move_scalars([t for t, _ in narrow], keep, remap, n, m)
+                else:
+                    idx = torch.as_tensor(keep_h).to(dev)
+                    for t in big + [t for t, _ in narrow]:
+                        t[:m] = t[idx]
+                    del idx
+                moved += (m - first) * sum(t.element_size() for t, _ in narrow)
+                if not kernel:
+                    moved += (m - first) * sum(t.shape[1] * t.element_size() for t in big)
+                for t in big:
+                    t[m:n] = 0
+                for t, fill in narrow:
+                    t[m:n] = fill
+                (T.rc_remap if kernel else T.rc_remap_ref)(esrc, edst, self.parent[:m], remap)
+            # ---- the k-means hierarchy follows (labels per row, rows per topic)
+            h = self._hier
+            if h:
+                nh = min(int(h["n"]), n)
+                kt = int(h["start"].numel()) - 1
+                sel = torch.nonzero(keep[:nh]).flatten()
+                pk = h["perm"][keep[h["perm"]] != 0]  # the kept members, still in (topic, row) order
+                start = torch.zeros_like(h["start"])
+                start[1:] = torch.cumsum(torch.bincount(h["top"][pk].long(), minlength=kt), 0)
+                h.update(fine=h["fine"][sel], top=h["top"][sel], perm=remap[pk].long(), start=start,
+                         n=int(sel.numel()))
+        # ---- host state
+        if hasattr(self.ids, "compact"):
+            for c in (self.ids, self.content, self.types):
+                c.compact(keep_h)
+        else:
+            kl = keep_h.tolist()
+            self.ids, self.content, self.types = ([c[r] for r in kl] for c in (self.ids, self.content, self.types))
+        self.row_of = dict(zip(self.ids.tolist() if hasattr(self.ids, "tolist") else self.ids, range(m)))
+        for name in ("children", "odd_emb"):
+            d = getattr(self, name)
+            if d:
+                ks = np.fromiter(d.keys(), dtype=np.int64, count=len(d))
+                setattr(self, name, {nk: d[k] for k, nk in zip(ks.tolist(), self._translate_once(ks, dead).tolist())
+                                     if nk >= 0})
+        lar = np.asarray(list(self.last_add_rows), dtype=np.int64)
+        self.last_add_rows = [r for r in self._translate_once(lar, dead).tolist() if r >= 0] if lar.size else range(0)
+        if views:
+            from ..models.graph import Node
+            cache = {}
+            for r, nr in zip(vr.tolist(), new_vr.tolist()):
+                v = views[r]
+                if nr >= 0:
+                    v.__dict__["_r"] = nr
+                    cache[nr] = v
+                else:  # what an evicted node is in the reference: a plain Node with its last values
+                    v.__dict__.clear()
+                    v.__class__ = Node
+                    v.__dict__.update(detach[r])
+            self._node_views = cache
+        self.n = m
+        self._reclaimed.append(dead)
+        self.row_epoch += 1
+        self.rows_reclaimed_total += n - m
+        # ---- everything derived from rows
+        self._bias_cache.clear()
+        self._mirror.clear()
+        self._csr, self._csr_version = None, -1
+        self._boost_state = T.BoostState()
+        self._ann_stale = True  # the IVF-PQ lists are keyed by row: rebuilt on next use
+        self._nodes_marked = False
+        if shrink:
+            cap = max(self._init_cap, math.ceil(1.1 * m))
+            if cap != self.cap:
+                with self.on_stream():
+                    self._alloc(cap)
+                for name in ("_rmb", "_dstamp"):  # sized by the capacity: re-made on next use
+                    if getattr(self, name, None) is not None:
+                        setattr(self, name, None)
+        self._bump(edges=True, store=True)
+        out.update(rows_after=m, reclaimed=n - m, capacity=self.cap, bytes_moved=int(moved), epoch=self.row_epoch)
+        return out
 
     # ------------------------------------------------------------------ persistence helpers
     def take_dirty_rows(self) -> np.ndarray:

@@ -188,27 +188,38 @@ class NodeList(Sequence):
     A :class:`NodeView` is made when an element is read, so a serving step
     that only passes results along allocates no Python object per row (the
     collector then has nothing new to walk; bench.py needs no gc.freeze).
-    Compares equal to a list of the same nodes."""
-    __slots__ = ("_g", "_rows")
+    Compares equal to a list of the same nodes. The rows carry the graph's
+    ``row_epoch``: after a row reclamation (``TenantGraph.compact``) they are
+    translated on the next read, and a reclaimed row drops out of the list."""
+    __slots__ = ("_g", "_rows", "_ep")
 
-    def __init__(self, g: TenantGraph, rows: np.ndarray):
+    def __init__(self, g: TenantGraph, rows: np.ndarray, epoch: Optional[int] = None):
         self._g, self._rows = g, rows
+        self._ep = g.row_epoch if epoch is None else epoch
+
+    def _sync(self) -> np.ndarray:
+        g = self._g
+        if self._ep != g.row_epoch:
+            r = g.translate_rows(self._rows, self._ep)
+            self._rows, self._ep = r[r >= 0], g.row_epoch
+        return self._rows
 
     @property
     def rows(self) -> np.ndarray:
-        return self._rows
+        return self._sync()
 
     def __len__(self) -> int:
-        return int(self._rows.shape[0])
+        return int(self._sync().shape[0])
 
     def __getitem__(self, i):
+        rows = self._sync()
         if isinstance(i, slice):
-            return [NodeView.of(self._g, r) for r in self._rows[i].tolist()]
-        return NodeView.of(self._g, int(self._rows[i]))
+            return [NodeView.of(self._g, r) for r in rows[i].tolist()]
+        return NodeView.of(self._g, int(rows[i]))
 
     def __iter__(self):
         g = self._g
-        for r in self._rows.tolist():
+        for r in self._sync().tolist():
             yield NodeView.of(g, r)
 
     def __eq__(self, other):
@@ -229,22 +240,31 @@ class NodeList(Sequence):
 class ResultBatch(Sequence):
     """A batch's search results: ``res[q]`` is query q's :class:`NodeList`.
     Holds the [nq, k] row array (-1 = empty slot or a row that is not a
-    node, marked on the device) and nothing per row."""
-    __slots__ = ("_g", "_rows")
+    node, marked on the device) and nothing per row. ``epoch``: the graph's
+    ``row_epoch`` the rows were found under (default: now); rows are
+    translated on read after a row reclamation (reclaimed rows become -1)."""
+    __slots__ = ("_g", "_rows", "_ep")
 
-    def __init__(self, g: TenantGraph, rows: np.ndarray):
+    def __init__(self, g: TenantGraph, rows: np.ndarray, epoch: Optional[int] = None):
         self._g, self._rows = g, np.asarray(rows, dtype=np.int64)
+        self._ep = g.row_epoch if epoch is None else epoch
+
+    def _sync(self) -> np.ndarray:
+        g = self._g
+        if self._ep != g.row_epoch:
+            self._rows, self._ep = g.translate_rows(self._rows, self._ep), g.row_epoch
+        return self._rows
 
     @property
     def rows(self) -> np.ndarray:
-        return self._rows
+        return self._sync()
 
     def __len__(self) -> int:
         return int(self._rows.shape[0])
 
     def _one(self, q: int) -> NodeList:
-        r = self._rows[q]
-        return NodeList(self._g, r[r >= 0])
+        r = self._sync()[q]
+        return NodeList(self._g, r[r >= 0], self._ep)
 
     def __getitem__(self, i):
         if isinstance(i, slice):
@@ -304,7 +324,8 @@ class EdgeView(Edge):
     @classmethod
     def of(cls, g: TenantGraph, shard_code: int, s: int, d: int, idx: int = -1) -> "EdgeView":
         v = object.__new__(cls)
-        v.__dict__.update(_g=g, _sc=shard_code, _s=s, _d=d, _i=idx, _ver=g.edge_version if idx >= 0 else -1)
+        v.__dict__.update(_g=g, _sc=shard_code, _s=s, _d=d, _i=idx, _ver=g.edge_version if idx >= 0 else -1,
+                          _ep=g.row_epoch)
         return v
 
     @classmethod
@@ -312,12 +333,22 @@ class EdgeView(Edge):
         if type(edge) is Edge:
             edge.__dict__.clear()
             edge.__class__ = cls
-            edge.__dict__.update(_g=g, _sc=shard_code, _s=s, _d=d, _i=-1, _ver=-1)
+            edge.__dict__.update(_g=g, _sc=shard_code, _s=s, _d=d, _i=-1, _ver=-1, _ep=g.row_epoch)
             return edge
         return cls.of(g, shard_code, s, d)
 
+    def _rows(self) -> Tuple[int, int]:
+        """The endpoint rows now: they follow a row reclamation (an edge's
+        endpoints are never reclaimed while the edge exists)."""
+        g = self._g
+        if self._ep != g.row_epoch:
+            s, d = g.translate_rows([self._s, self._d], self._ep).tolist()
+            self.__dict__.update(_s=s, _d=d, _ep=g.row_epoch, _ver=-1)
+        return self._s, self._d
+
     def _idx(self) -> int:
         g = self._g
+        self._rows()
         if self._ver != g.edge_version or self._i < 0:
             self.__dict__["_i"] = g.edge_index(self._s, self._d, self._sc)
             self.__dict__["_ver"] = g.edge_version
@@ -339,8 +370,8 @@ class EdgeView(Edge):
             g._bump(edges=True)
             self.__dict__["_ver"] = g.edge_version
 
-    source = property(lambda self: self._g.ids[self._s])
-    target = property(lambda self: self._g.ids[self._d])
+    source = property(lambda self: self._g.ids[self._rows()[0]])
+    target = property(lambda self: self._g.ids[self._rows()[1]])
     weight = property(lambda self: float(self._get("w")), lambda self, v: self._set("w", float(v)))
     co_occurrence = property(lambda self: int(self._get("co")), lambda self, v: self._set("co", int(v)))
     last_updated = property(lambda self: float(self._get("lu")), lambda self, v: self._set("lu", float(v)))
@@ -357,7 +388,7 @@ class EdgeView(Edge):
 
     def __eq__(self, other):
         if isinstance(other, EdgeView):
-            return (self._g is other._g and self._sc == other._sc and self._s == other._s and self._d == other._d)
+            return self._g is other._g and self._sc == other._sc and self._rows() == other._rows()
         return Edge.__eq__(self, other)
 
     __hash__ = object.__hash__

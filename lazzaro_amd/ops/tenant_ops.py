@@ -761,3 +761,155 @@ def write_emb(g, e32: torch.Tensor, has: Optional[torch.Tensor], rows: Optional[
         g.has_emb.data_ptr() if has_emb else None, _lib.stream_ptr(x.device)), "lzk_tg_write_emb")
     if g.emb8 is not None and not i8:  # fp8 copy: the torch quantiser
         g._write_lowp(r, x * h[:, None].to(x.dtype) if h is not None else x)
+
+
+# ---------------------------------------------------------------- row reclamation (csrc/kernels/compact.hip)
+_lib.register("lzk_rc_mark", I, [P, P, P, P, L, P, P, L, P, P])
+_lib.register("lzk_rc_move_rows", I, [P, L, P, P, L, L, L, P, P, L, P, P])
+_lib.register("lzk_rc_move_scalars", I, [P, I, P, P, L, P])
+_lib.register("lzk_rc_remap", I, [P, P, L, P, L, P, L, P])
+
+# the bounce buffer of an in-place column move holds at most this many bytes
+RC_BOUNCE_BYTES = 256 << 20
+
+
+def rc_mark(kind: torch.Tensor, stored: torch.Tensor, dirty: torch.Tensor, parent: torch.Tensor,
+            src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
+    """uint8 keep flags of the rows [0, n) for a row reclamation: a row stays
+    if it is a node, a store row or dirty, an endpoint of an edge, or the
+    parent of a row that stays (compact.hip rc_mark_* kernels)."""
+    n = int(kind.numel())
+    if not kind.is_cuda:
+        return rc_mark_ref(kind, stored, dirty, parent, src, dst)
+    keep = torch.empty(n, dtype=torch.uint8, device=kind.device)
+    ne = int(src.numel())
+    assert src.dtype == torch.int32 and dst.dtype == torch.int32 and parent.dtype == torch.int32
+    _lib.check(_lib.lib().lzk_rc_mark(kind.data_ptr(), stored.data_ptr(), dirty.data_ptr(), parent.data_ptr(), n,
+                                      src.data_ptr() if ne else None, dst.data_ptr() if ne else None, ne,
+                                      keep.data_ptr(), _st(kind)), "rc_mark")
+    return keep
+
+
+def rc_mark_ref(kind, stored, dirty, parent, src, dst) -> torch.Tensor:
+    """The torch formulation of :func:`rc_mark` (any device)."""
+    n = int(kind.numel())
+    keep = (kind == 1) | (stored != 0) | (dirty != 0)
+    if src.numel():
+        keep[src.long()] = True
+        keep[dst.long()] = True
+    while True:  # parents of kept rows, to the fixed point (chains of ghost parents)
+        p = parent[keep].long()
+        p = p[(p >= 0) & (p < n)]
+        p = p[~keep[p]]
+        if p.numel() == 0:
+            break
+        keep[p] = True
+    return keep.to(torch.uint8)
+
+
+def rc_remap_of(keep: torch.Tensor) -> torch.Tensor:
+    """int32 [n + 1]: the exclusive prefix sum of the keep flags -- a kept
+    row's new index; entry n is the number of kept rows."""
+    n = int(keep.numel())
+    remap = torch.zeros(n + 1, dtype=torch.int32, device=keep.device)
+    if n:
+        torch.cumsum(keep, 0, dtype=torch.int32, out=remap[1:])
+    return remap
+
+
+def rc_chunk_rows(row_bytes: int) -> int:
+    """Rows per chunk of an in-place move whose bounce buffer stays within RC_BOUNCE_BYTES."""
+    return max(1024, RC_BOUNCE_BYTES // max(1, int(row_bytes)))
+
+
+def rc_bounds(remap: torch.Tensor, n: int, first: int, chunk_rows: int) -> np.ndarray:
+    """remap at the chunk boundaries first, first + chunk_rows, ..., n (host
+    int32): what the in-place schedule of :func:`rc_move_rows` decides by."""
+    idx = list(range(first, n, chunk_rows)) + [n]
+    return remap[torch.as_tensor(idx, dtype=torch.long).to(remap.device)].cpu().numpy().astype(np.int32)
+
+
+def rc_move_rows(col: torch.Tensor, keep: torch.Tensor, remap: torch.Tensor, n: int, first: int,
+                 chunk_rows: int, bounds: Optional[np.ndarray] = None,
+                 bounce: Optional[torch.Tensor] = None) -> Tuple[int, int, int]:
+    """Move the kept rows of ``col[:n]`` down to ``col[:remap[n]]`` in place
+    and in order (compact.hip rc_move_rows_kernel; the chunk schedule and why
+    it is safe are described there). ``first``: the first dead row (rows
+    before it stay). ``bounce``: a uint8 device buffer of at least chunk_rows
+    x row bytes (allocated here when missing). Returns (bytes moved, chunks
+    written directly, chunks through the bounce buffer). CPU tensors:
+    :func:`rc_move_rows_ref`."""
+    if not col.is_cuda:
+        m = rc_move_rows_ref(col, keep, n)
+        return (m - first) * col[0].numel() * col.element_size() if m > first else 0, 0, 0
+    assert col.is_contiguous()
+    row_bytes = (col.numel() // col.shape[0]) * col.element_size() if col.shape[0] else 0
+    if n == 0 or first >= n or row_bytes == 0:
+        return 0, 0, 0
+    if bounds is None:
+        bounds = rc_bounds(remap, n, first, chunk_rows)
+    need = min(chunk_rows, n - first) * row_bytes
+    if bounce is None or bounce.numel() < need:
+        bounce = torch.empty(need, dtype=torch.uint8, device=col.device)
+    bounds = np.ascontiguousarray(bounds, dtype=np.int32)
+    assert len(bounds) == (n - first + chunk_rows - 1) // chunk_rows + 1
+    stats = np.zeros(3, np.int64)
+    _lib.check(_lib.lib().lzk_rc_move_rows(col.data_ptr(), row_bytes, keep.data_ptr(), remap.data_ptr(), n, first,
+                                           int(chunk_rows), bounds.ctypes.data, bounce.data_ptr(),
+                                           int(bounce.numel()), stats.ctypes.data, _st(col)), "rc_move_rows")
+    return int(stats[0]), int(stats[1]), int(stats[2])
+
+
+def rc_move_rows_ref(col: torch.Tensor, keep: torch.Tensor, n: int) -> int:
+    """The torch formulation of :func:`rc_move_rows` (out of place: the
+    gather makes a second copy of the kept rows). Returns the kept count."""
+    idx = torch.nonzero(keep[:n]).flatten()
+    m = int(idx.numel())
+    if m < n:
+        col[:m] = col[idx]
+    return m
+
+
+def rc_move_scalars(cols: Sequence[torch.Tensor], keep: torch.Tensor, remap: torch.Tensor, n: int, m: int) -> None:
+    """The narrow per-row columns (1, 4 or 8 bytes per row) through the same
+    remap: every column gathered into a temporary in one launch
+    (compact.hip rc_move_scalars_kernel), then copied back over [0, m)."""
+    if not cols or n == 0:
+        return
+    if not cols[0].is_cuda:
+        for c in cols:
+            rc_move_rows_ref(c, keep, n)
+        return
+    for a in range(0, len(cols), 16):
+        part = list(cols[a:a + 16])
+        tmp = [torch.empty(m, dtype=c.dtype, device=c.device) for c in part]
+        tab = np.asarray([[c.data_ptr(), t.data_ptr(), c.element_size()] for c, t in zip(part, tmp)], dtype=np.int64)
+        _lib.check(_lib.lib().lzk_rc_move_scalars(tab.ctypes.data, len(part), keep.data_ptr(), remap.data_ptr(), n,
+                                                  _st(keep)), "rc_move_scalars")
+        for c, t in zip(part, tmp):
+            c[:m].copy_(t)
+
+
+def rc_remap(src: torch.Tensor, dst: torch.Tensor, parent: Optional[torch.Tensor], remap: torch.Tensor) -> None:
+    """Edge endpoints and the parent values of the (already moved) rows
+    through ``remap``, in place (compact.hip rc_remap_* kernels). Every
+    referenced row was kept by :func:`rc_mark`."""
+    n_old = int(remap.numel()) - 1
+    if not remap.is_cuda:
+        return rc_remap_ref(src, dst, parent, remap)
+    ne = int(src.numel())
+    npar = int(parent.numel()) if parent is not None else 0
+    _lib.check(_lib.lib().lzk_rc_remap(src.data_ptr() if ne else None, dst.data_ptr() if ne else None, ne,
+                                       parent.data_ptr() if npar else None, npar, remap.data_ptr(), n_old,
+                                       _st(remap)), "rc_remap")
+
+
+def rc_remap_ref(src: torch.Tensor, dst: torch.Tensor, parent: Optional[torch.Tensor], remap: torch.Tensor) -> None:
+    """The torch formulation of :func:`rc_remap` (any device)."""
+    n_old = int(remap.numel()) - 1
+    if src.numel():
+        src.copy_(remap[src.long()])
+        dst.copy_(remap[dst.long()])
+    if parent is not None and parent.numel():
+        ok = (parent >= 0) & (parent < n_old)
+        parent.copy_(torch.where(ok, remap[parent.clamp(0, max(n_old - 1, 0)).long()], parent))

@@ -270,7 +270,10 @@ def local_search(svc, users: Sequence[str], Q: torch.Tensor, limits: Sequence[in
 class RoutedHits:
     """Result of :func:`search_routed`, in the caller's query order:
     ``scores`` fp32 [n, k] and ``rows`` int64 [n, k] (-1 = no hit) on the
-    caller's device, ``owner`` the rank holding each query's tenant."""
+    caller's device, ``owner`` the rank holding each query's tenant. The rows
+    are the owners' rows at search time and carry no row epoch (they may
+    belong to another rank's graph): resolve them before the owning tenant
+    reclaims rows (``TenantGraph.compact``)."""
     users: List[str]
     owner: List[int]
     scores: torch.Tensor
@@ -487,7 +490,8 @@ class GlobalHits:
     """:func:`search_global_batch` result: ``scores`` [b, k]; ``keys`` [b, k]
     int64 = rank << 56 | tenant slot << 32 | row (-1 = none) -- the merge's
     total order; a slot is only meaningful on its rank at search time (slots
-    are recycled when tenants leave). ``tenant_keys`` [b, k] int64 is the
+    are recycled when tenants leave, and a row only until its tenant reclaims
+    rows -- ``TenantGraph.compact``). ``tenant_keys`` [b, k] int64 is the
     stable 63-bit :func:`tenant_key` of each hit's tenant (-1 = none):
     :meth:`users` maps them to names."""
     scores: torch.Tensor

@@ -64,16 +64,19 @@ class SearchHits(_SeqABC):
     result of a tenant before it runs a mutating request on it (or releases
     / migrates it), so a late read still sees the rows as they were; a
     caller that mutates a tenant directly (``svc.system(u).chat(...)``)
-    should read its results first."""
-    __slots__ = ("_g", "_cols", "_q", "_limit", "_items", "__weakref__")
+    should read its results first. The rows carry the graph's ``row_epoch``
+    and are translated when read after a row reclamation
+    (``TenantGraph.compact``); a reclaimed row drops out."""
+    __slots__ = ("_g", "_cols", "_q", "_limit", "_items", "_ep", "__weakref__")
 
     def __init__(self, g, cols: Dict[str, np.ndarray], q: int, limit: int):
         self._g, self._cols, self._q, self._limit, self._items = g, cols, q, limit, None
+        self._ep = g.row_epoch
 
     def _mat(self) -> List[Dict]:
         if self._items is None:
             c, q, L, g = self._cols, self._q, self._limit, self._g
-            rq, kq = c["rows"][q, :L].tolist(), c["kind"][q, :L].tolist()
+            rq, kq = g.translate_rows(c["rows"][q, :L], self._ep).tolist(), c["kind"][q, :L].tolist()
             sq, aq = c["sal"][q, :L].tolist(), c["acc"][q, :L].tolist()
             pq, hq = c["sup"][q, :L].tolist(), c["shard"][q, :L].tolist()
             ids, content, types, names = g.ids, g.content, g.types, g.shard_names

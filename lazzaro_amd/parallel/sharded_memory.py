@@ -142,7 +142,14 @@ class ShardedMemorySystem:
     is held by the home rank of its fine cluster (the rank holding most of
     that cluster's rows) instead of the rank whose conversation made it, so
     topics stay together and the pruned scan stays ~(own facts) x (own
-    rows) as ranks are added. Neither changes a decision."""
+    rows) as ranks are added. Neither changes a decision.
+
+    Row reclamation (``TenantGraph.compact`` / ``MemorySystem.compact_memory``)
+    is NOT available here: the global-number index of a row-sharded tenant
+    holds local rows of every rank's graph, and nothing translates it. This
+    class never calls ``compact`` and its ranks' local systems must be built
+    without ``compact_dead_fraction``; a row-sharded tenant's rows still only
+    grow."""
 
     def __init__(self, comm: Optional[Communicator] = None, user_id: str = "default", *,
                  max_buffer_size: int = 10, consolidate_every: int = 3, auto_consolidate: bool = True,
