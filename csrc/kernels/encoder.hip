@@ -769,7 +769,27 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const u16* __restrict__ 
 // scale, exactly what quant_fp8_rows_kernel makes of the bf16 output (amax of
 // the bf16-rounded values / 448) -- the next projection's input without the
 // separate quantise pass (one read + one write of the activations per GEMM).
-template <int C, bool RES, int RPW, bool Q8 = false>
+// V16 false: rows that are only 8-B aligned (a leading dimension that is a
+// multiple of 4 but not of 8) move each chunk as two 8-B halves. Lane -> column
+// mapping, summation order and arithmetic are the same, so the result of a row
+// does not depend on the alignment of its buffers.
+template <bool V16>
+__device__ __forceinline__ u16x8 ln_load8(const u16* p) {
+  if constexpr (V16) return *reinterpret_cast<const u16x8*>(p);
+  const u16x4 lo = *reinterpret_cast<const u16x4*>(p), hi = *reinterpret_cast<const u16x4*>(p + 4);
+  return u16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+}
+template <bool V16>
+__device__ __forceinline__ void ln_store8(u16* p, const u16x8& v) {
+  if constexpr (V16) {
+    *reinterpret_cast<u16x8*>(p) = v;
+  } else {
+    *reinterpret_cast<u16x4*>(p) = u16x4{v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<u16x4*>(p + 4) = u16x4{v[4], v[5], v[6], v[7]};
+  }
+}
+
+template <int C, bool RES, int RPW, bool Q8 = false, bool V16 = true>
 __global__ __launch_bounds__(256) void layernorm16_kernel(const u16* __restrict__ X, long ldx,
                                                           const u16* __restrict__ R, long ldr,
                                                           const float* __restrict__ g,
@@ -789,9 +809,9 @@ __global__ __launch_bounds__(256) void layernorm16_kernel(const u16* __restrict_
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       const int col = c * 256 + l32 * 8;
-      const u16x8 x = *reinterpret_cast<const u16x8*>(X + (long)row * ldx + col);
+      const u16x8 x = ln_load8<V16>(X + (long)row * ldx + col);
       u16x8 r = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (RES) r = *reinterpret_cast<const u16x8*>(R + (long)row * ldr + col);
+      if (RES) r = ln_load8<V16>(R + (long)row * ldr + col);
 #pragma unroll
       for (int u = 0; u < 8; ++u) v[rr][c][u] = bf16_to_f32(x[u]) + (RES ? bf16_to_f32(r[u]) : 0.f);
     }
@@ -832,7 +852,7 @@ __global__ __launch_bounds__(256) void layernorm16_kernel(const u16* __restrict_
 #pragma unroll
         for (int u = 0; u < 8; ++u) amax = fmaxf(amax, fabsf(bf16_to_f32(ov[c][u])));
       }
-      if (row < rows) *reinterpret_cast<u16x8*>(Y + (long)row * ldy + col) = ov[c];
+      if (row < rows) ln_store8<V16>(Y + (long)row * ldy + col, ov[c]);
     }
     if (Q8) {
 #pragma unroll
@@ -1209,22 +1229,26 @@ LZK_EXPORT int lzk_layernorm(const void* X, long ldx, const void* R, long ldr, c
   const u16* x = (const u16*)X;
   const u16* r = (const u16*)R;
   u16* y = (u16*)Y;
-  const bool v16 = (H == 768 || H == 1024) && ldx % 8 == 0 && ldy % 8 == 0 && (!r || ldr % 8 == 0) &&
-                   ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) |
-                     reinterpret_cast<uintptr_t>(R)) & 15) == 0;
-  if (v16) {
+  const uintptr_t ptrs = reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(R);
+  const bool h16 = H == 768 || H == 1024;
+  const bool v16 = h16 && ldx % 8 == 0 && ldy % 8 == 0 && (!r || ldr % 8 == 0) && (ptrs & 15) == 0;
+  // 8-B aligned rows only: the same kernel with 8-B accesses (same result as the 16-B one)
+  const bool v8 = h16 && ldx % 4 == 0 && ldy % 4 == 0 && (!r || ldr % 4 == 0) && (ptrs & 7) == 0;
+  if (v16 || v8) {
     constexpr int RP = 2;  // row pairs per wave -> 16 rows per 256-thread block
     dim3 grid16((rows + 16 - 1) / 16);
-#define LN16(C)                                                                                                 \
-  do {                                                                                                          \
-    if (r) hipLaunchKernelGGL((layernorm16_kernel<C, true, RP>), grid16, block, 0, st, x, ldx, r, ldr, g, b,    \
-                              rows, eps, y, ldy);                                                               \
-    else hipLaunchKernelGGL((layernorm16_kernel<C, false, RP>), grid16, block, 0, st, x, ldx, r, ldr, g, b,     \
-                            rows, eps, y, ldy);                                                                 \
+#define LN16V(C, RS, V)                                                                                         \
+  hipLaunchKernelGGL((layernorm16_kernel<C, RS, RP, false, V>), grid16, block, 0, st, x, ldx, r, ldr, g, b,     \
+                     rows, eps, y, ldy, (unsigned char*)nullptr, 0L, (float*)nullptr)
+#define LN16(C)                                             \
+  do {                                                      \
+    if (v16) { if (r) LN16V(C, true, true); else LN16V(C, false, true); }   \
+    else { if (r) LN16V(C, true, false); else LN16V(C, false, false); }     \
   } while (0)
     if (H == 768) LN16(3);
     else LN16(4);
 #undef LN16
+#undef LN16V
     return (int)hipGetLastError();
   }
 #define LN(NC)                                                                                                  \
