@@ -756,7 +756,8 @@ class MemorySystem(ConsolidationMixin):
         sq, sms = m.get("search_queries", 0), m.get("search_ms", 0.0)
         return {"device": str(self._device), "graph_rows": g.n, "hbm_graph_bytes": self._graph_bytes(),
                 "dead_rows": g.n - g.num_nodes(), "row_epoch": g.row_epoch,
-                "rows_reclaimed_total": g.rows_reclaimed_total, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
+                "rows_reclaimed_total": g.rows_reclaimed_total, "ann_removed": g.ann_removed,
+                "ann_upserts": g.ann_upserts, "ann_rebuilds": g.ann_rebuilds, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
                 "avg_search_batch_ms": round(sms / m["search_batches"], 3) if m.get("search_batches") else 0.0}
 
     def _graph_bytes(self) -> int:

@@ -370,6 +370,13 @@ class TenantGraph:
         self._ann = None
         self._ann_covered = 0
         self._ann_stale = False
+        # index maintenance (see _ann_candidates): indexed rows whose vector was
+        # rewritten, the rows already removed from the index (uint8 per covered
+        # row) and the store version the dead rows were last synced at
+        self._ann_pending: set = set()
+        self._ann_dead: Optional[torch.Tensor] = None
+        self._ann_synced = -1
+        self.ann_removed = self.ann_upserts = self.ann_rebuilds = 0
         self.lock = threading.RLock()
         z = lambda dt: torch.zeros(0, dtype=dt, device=self.device)  # noqa: E731
         self.e = {"src": z(torch.int32), "dst": z(torch.int32), "w": z(torch.float32), "co": z(torch.int32),
@@ -691,7 +698,7 @@ class TenantGraph:
                     self.row_of[i] = r
                 else:
                     if r < self._ann_covered:
-                        self._ann_stale = True  # re-added id: its row gets a new vector
+                        self._ann_pending.add(r)  # re-added id: its row gets a new vector (upsert on next search)
                     if kind_h is not None and r < len(kind_h) and kind_h[r] == NODE:
                         self._unlink_row(r)
                     self.content[r] = contents[j]
@@ -1120,7 +1127,7 @@ class TenantGraph:
     def set_embedding(self, r: int, emb) -> None:
         self.odd_emb.pop(r, None)
         if r < self._ann_covered:
-            self._ann_stale = True  # an indexed row's vector changed: rebuild the IVF-PQ codes
+            self._ann_pending.add(r)  # an indexed row's vector changed: re-encoded on the next search
         if emb is None or len(emb) == 0:
             if self.dim is not None:
                 with self.on_stream():
@@ -2465,12 +2472,23 @@ class TenantGraph:
     def _ann_candidates(self, Qf: torch.Tensor, R: int, cfg: Dict) -> torch.Tensor:
         """Graph rows [M, R] from the tenant's IVF-PQ index, built on first
         use over the unit rows (ids = rows) and extended with the rows
-        appended since; rebuilt when an embedding was rewritten in place.
-        Removed / unstored rows stay in the index and are dropped by the
-        re-rank's -inf bias."""
+        appended since, and maintained in place from then on (no re-train,
+        no re-encode of the rest):
+
+        * a row whose embedding was rewritten, or whose id was added again
+          (``_ann_pending``), is upserted -- or removed if it lost its vector;
+        * rows that left the store for good -- GHOST or FREE with the stored
+          bit clear, which only ``add_nodes`` of their id brings back -- are
+          removed from the lists, so they take no candidate slot (one
+          elementwise pass, only when the store version moved);
+        * :meth:`compact` renumbers the index's ids through its row remap.
+
+        Rebuilt only for what that cannot express: a reload, or rows that
+        vanished without a compaction (``_ann_covered > n``)."""
         from ..index.ivfpq import IVFPQIndex
         n = self.n
         idx = self._ann
+        dev = self.device
         if idx is None or self._ann_stale or self._ann_covered > n:
             m = cfg["m"] if self.dim % cfg["m"] == 0 else next(d for d in (64, 48, 32, 16, 8) if self.dim % d == 0)
             nlist = max(16, min(cfg["nlist"], n // 64))
@@ -2480,13 +2498,48 @@ class TenantGraph:
             pick = live[torch.randperm(live.numel(), generator=g)[: min(live.numel(), 262144)].to(live.device)]
             idx.train(self.emb32[pick], iters=8, pq_iters=8)
             idx.reserve(n)
+            self.ann_rebuilds += self._ann is not None  # (the first build is not a rebuild)
             self._ann, self._ann_covered, self._ann_stale = idx, 0, False
+            self._ann_pending, self._ann_dead, self._ann_synced = set(), None, -1
+        elif self._ann_pending:
+            c = self._ann_covered
+            rows = torch.as_tensor(sorted(r for r in self._ann_pending if r < c), dtype=torch.long).to(dev)
+            self._ann_pending = set()
+            if rows.numel():
+                has = self.has_emb[rows] == 1
+                up, gone = rows[has], rows[~has]
+                dead = self._ann_dead_flags(c)
+                if up.numel():
+                    idx.upsert(up, self.emb32[up])
+                    dead[up] = 0
+                    self.ann_upserts += int(up.numel())
+                if gone.numel():
+                    self.ann_removed += idx.remove(gone)
+                    dead[gone] = 1
         step = 1 << 20
         while self._ann_covered < n:
             r1 = min(n, self._ann_covered + step)
             idx.add(self.emb32[self._ann_covered:r1], ids=torch.arange(self._ann_covered, r1))
             self._ann_covered = r1
+        if self._ann_synced != self._store_version:
+            dead = self._ann_dead_flags(n)
+            k = self.kind[:n]
+            rows = torch.nonzero(((k == GHOST) | (k == FREE)) & (self.stored[:n] == 0) & (dead[:n] == 0)).flatten()
+            if rows.numel():
+                self.ann_removed += idx.remove(rows)
+                dead[rows] = 1
+            self._ann_synced = self._store_version
         return idx.candidate_ids(Qf, R, cfg["nprobe"])
+
+    def _ann_dead_flags(self, c: int) -> torch.Tensor:
+        """uint8 per indexed row: 1 = already removed from the IVF-PQ index."""
+        d = self._ann_dead
+        if d is None or d.numel() < c:
+            grown = torch.zeros(max(c, self.cap), dtype=torch.uint8, device=self.device)
+            if d is not None:
+                grown[: d.numel()] = d
+            self._ann_dead = d = grown
+        return d
 
     def _lowp_exact(self, default: bool) -> bool:
         m = getattr(self, "LOWP_EXACT_MODE", None) or LOWP_EXACT
@@ -2859,7 +2912,8 @@ class TenantGraph:
         RC_BOUNCE_BYTES); COMPACT_KERNEL = False and the CPU take the torch
         formulation. ``shrink``: then re-allocate to max(initial capacity,
         ceil(1.1 n)) rows. The IVF-PQ index of a large store, keyed by row,
-        is rebuilt on its next use. Not while a segment or an incremental
+        is renumbered through the remap (IVFPQIndex.translate_ids), not
+        rebuilt. Not while a segment or an incremental
         components window is open. Holders of rows: see :meth:`translate_rows`.
 
         Returns rows_before, rows_after, reclaimed, ghosts_kept, capacity,
@@ -2928,6 +2982,22 @@ class TenantGraph:
                 for t, fill in narrow:
                     t[m:n] = fill
                 (T.rc_remap if kernel else T.rc_remap_ref)(esrc, edst, self.parent[:m], remap)
+            # ---- the IVF-PQ index is keyed by row: its ids follow the remap, the
+            # reclaimed rows leave its lists (in place, at its next search)
+            if self._ann is not None and not self._ann_stale and self._ann_covered <= n:
+                c = self._ann_covered
+                self._ann.translate_ids(torch.where(keep != 0, remap[:n].long(), torch.full_like(remap[:n], -1,
+                                                                                               dtype=torch.long)))
+                if self._ann_dead is not None:
+                    d = self._ann_dead_flags(c)[:c][keep[:c] != 0]
+                    self._ann_dead = torch.zeros(max(self.cap, int(d.numel())), dtype=torch.uint8, device=dev)
+                    self._ann_dead[: d.numel()] = d
+                self._ann_covered = int(remap[c])  # the kept rows below the old mark
+                if self._ann_pending:
+                    pr = self._translate_once(np.asarray(sorted(self._ann_pending), dtype=np.int64), dead)
+                    self._ann_pending = set(int(r) for r in pr.tolist() if r >= 0)
+            else:
+                self._ann_stale = self._ann is not None
             # ---- the k-means hierarchy follows (labels per row, rows per topic)
             h = self._hier
             if h:
@@ -2977,7 +3047,6 @@ class TenantGraph:
         self._mirror.clear()
         self._csr, self._csr_version = None, -1
         self._boost_state = T.BoostState()
-        self._ann_stale = True  # the IVF-PQ lists are keyed by row: rebuilt on next use
         self._nodes_marked = False
         if shrink:
             cap = max(self._init_cap, math.ceil(1.1 * m))

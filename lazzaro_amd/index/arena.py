@@ -340,8 +340,9 @@ class ArenaIVF:
 
     Row indices of the arena are the index ids, so the PQ candidates are
     re-ranked exactly against the arena's rows (fp32 copy when kept) with the
-    arena's metric and tombstones. Appends are encoded incrementally; a clear
-    or compaction (row indices change) triggers a rebuild on the next search.
+    arena's metric and tombstones. Appends are encoded incrementally and
+    tombstoned rows are removed from the lists in place; a clear or compaction
+    (row indices change) triggers a rebuild on the next search.
     """
 
     def __init__(self, arena: VectorArena, nlist: int, m: int, nprobe: int, min_rows: int, candidates: int):
@@ -350,6 +351,8 @@ class ArenaIVF:
         self.idx = None
         self.epoch = -1
         self.covered = 0
+        self.dead = None  # per covered row: already removed from the index
+        self.synced = -1  # the arena version the tombstones were last synced at
 
     def _rows(self, r0: int, r1: int) -> torch.Tensor:
         a = self.arena
@@ -368,11 +371,26 @@ class ArenaIVF:
             self.idx.train(self._rows(0, a.n)[pick], iters=8, pq_iters=8)
             self.covered = 0
             self.epoch = a.layout_epoch
+            self.dead, self.synced = None, -1
         step = 1 << 20
         while self.covered < a.n:
             r1 = min(a.n, self.covered + step)
             self.idx.add(self._rows(self.covered, r1), ids=torch.arange(self.covered, r1))
             self.covered = r1
+        if self.synced != a.version:
+            # rows tombstoned since the last sync leave the lists (IVFPQIndex.remove),
+            # so they take none of the ``candidates`` slots
+            c = self.covered
+            if self.dead is None or self.dead.numel() < c:
+                grown = torch.zeros(max(c, a.cap), dtype=torch.bool, device=a.device)
+                if self.dead is not None:
+                    grown[: self.dead.numel()] = self.dead
+                self.dead = grown
+            rows = torch.nonzero(torch.isneginf(a.bias[:c]) & ~self.dead[:c]).flatten()
+            if rows.numel():
+                self.idx.remove(rows)
+                self.dead[rows] = True
+            self.synced = a.version
 
     def search(self, qf: torch.Tensor, k: int, metric: str):
         self.sync()

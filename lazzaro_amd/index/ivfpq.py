@@ -15,6 +15,15 @@ storage. Inner-product metric on unit vectors (cosine).
           ``topk_merge`` kernel; deep lists (re-rank depth > 16) from
           ``ivfpq_scan_deep`` (each wave's best rows per list); optional exact
           re-rank of the candidates against kept bf16/fp8 rows.
+* maintain: ``remove(ids)``, ``upsert(ids, x)`` and ``translate_ids(table)``
+          delete, rewrite and renumber vectors without a re-train or a
+          re-encode of the rest. They only flag rows and append code rows; the
+          next search's ``_finalize`` squeezes the flagged rows out in place
+          (compact.hip) and merges the appended tail into the CSR order by
+          opening gaps in place (ivfmaint.hip) -- O(n) bytes moved, no sort
+          and no second code buffer. ``_finalize_ref`` is the torch
+          formulation (stable full sort) that the kernel path equals bit for
+          bit. Ids are unique among the live vectors.
 CPU tensors run a torch reference of the same pipeline (tests).
 """
 from __future__ import annotations
@@ -42,6 +51,11 @@ _lib.register("lzk_rerank", _lib.I, [_lib.P, _lib.L, _lib.I, _lib.P, _lib.P, _li
                                       _lib.I, _lib.I, _lib.P, _lib.P, _lib.P])
 
 KSLOTS = (1, 4, 10, 16)
+
+# _finalize on the GPU: flagged rows leave and the appended tail is merged in
+# place by the HIP kernels (compact.hip, ivfmaint.hip); MAINT_KERNEL = False:
+# the torch formulation the CPU runs (a stable sort of every row)
+MAINT_KERNEL = True
 
 
 def _kslot(k: int) -> int:
@@ -78,8 +92,15 @@ class IVFPQIndex:
         self.keep_vectors = "bf16" if keep_vectors is True else (keep_vectors or False)
         if self.keep_vectors not in (False, "bf16", "fp8", "int8"):
             raise ValueError("keep_vectors must be False, True/'bf16', 'int8' or 'fp8'")
-        self.n = 0
+        self.n = 0   # code rows (codes, list_of, pos)
+        self.nv = 0  # vector rows (ids, re-rank copy); == n except while changes are pending
         self.cap = 0
+        self._sorted_n = 0  # the prefix of the code rows in CSR order, described by list_off
+        self._cdead = None  # pending: uint8 per code row / per vector row, 1 = leaves at
+        self._vdead = None  # the next _finalize (allocated on first use, dropped there)
+        self._nlive = 0
+        self.chunk_rows = None  # rows per chunk of the in-place moves (None: rc_chunk_rows)
+        self.last_maint = None  # what the last in-place _finalize moved (bytes, direct / bounced chunks)
         z = lambda *s, dt: torch.zeros(s, dtype=dt, device=self.device)  # noqa: E731
         self._codes = z(0, m, dt=torch.uint8)
         self._list = z(0, dt=torch.int32)
@@ -97,7 +118,7 @@ class IVFPQIndex:
         if n <= self.cap:
             return
         cap = max(n, int(self.cap * 1.5) + 1)
-        k = self.n
+        k = max(self.n, self.nv)
 
         def grow(t, shape, dt):
             new = torch.zeros(shape, dtype=dt, device=self.device)
@@ -114,6 +135,10 @@ class IVFPQIndex:
         elif self.keep_vectors in ("fp8", "int8"):
             self._vec = grow(self._vec, (cap, self.dim), torch.uint8)
             self._vscale = grow(self._vscale, (cap,), torch.float32)
+        if self._cdead is not None:
+            self._cdead = grow(self._cdead, (cap,), torch.uint8)
+        if self._vdead is not None:
+            self._vdead = grow(self._vdead, (cap,), torch.uint8)
         self.cap = cap
 
     # views of the live rows (code order) -- and setters for hand-built indexes
@@ -125,6 +150,9 @@ class IVFPQIndex:
     def codes(self, v: torch.Tensor) -> None:
         self._codes, self.n, self.cap = v.to(self.device), v.shape[0], v.shape[0]
         self._pos = torch.arange(self.n, device=self.device)
+        # a hand-built index is in CSR order already (list_off is set beside it)
+        self.nv = self._sorted_n = self._nlive = self.n
+        self._cdead = self._vdead = None
 
     @property
     def list_of(self) -> torch.Tensor:
@@ -146,11 +174,11 @@ class IVFPQIndex:
 
     @property
     def vectors(self):
-        return None if self._vec is None else self._vec[: self.n]
+        return None if self._vec is None else self._vec[: self.nv]
 
     @property
     def vscale(self):
-        return None if self._vscale is None else self._vscale[: self.n]
+        return None if self._vscale is None else self._vscale[: self.nv]
 
     # ------------------------------------------------------------------ train
     def _pad(self, x: torch.Tensor) -> torch.Tensor:
@@ -207,41 +235,173 @@ class IVFPQIndex:
         return lab, codes
 
     def add(self, x: torch.Tensor, ids: Optional[torch.Tensor] = None, batch: int = 1 << 18) -> None:
-        n0 = self.n
         n = x.shape[0]
-        self.reserve(n0 + n)
-        ids = torch.arange(n0, n0 + n, dtype=torch.int64) if ids is None else ids.to(torch.int64)
-        self._vids[n0:n0 + n] = ids.to(self.device)
-        self._pos[n0:n0 + n] = torch.arange(n0, n0 + n, device=self.device)
+        ids = torch.arange(self.n, self.n + n, dtype=torch.int64) if ids is None else ids.to(torch.int64)
+        self._append(x, ids, None, batch)
+
+    def _append(self, x: torch.Tensor, ids: Optional[torch.Tensor], vrows: Optional[torch.Tensor],
+                batch: int = 1 << 18) -> None:
+        """Encode ``x`` into new code rows at the tail. ``vrows`` None: new
+        vector rows with ``ids`` behind the existing ones (``add``); else the
+        vector rows (int64, on the device) whose kept copy is overwritten and
+        which the new code rows point at (``upsert`` of held ids)."""
+        n0, v0 = self.n, self.nv
+        n = x.shape[0]
+        fresh = vrows is None
+        self.reserve(max(n0 + n, v0 + (n if fresh else 0)))
+        if fresh:
+            self._vids[v0:v0 + n] = ids.to(self.device)
+            self._pos[n0:n0 + n] = torch.arange(v0, v0 + n, device=self.device)
+        else:
+            self._pos[n0:n0 + n] = vrows
         for r0 in range(0, n, batch):
             r1 = min(n, r0 + batch)
             xb = _unit(x[r0:r1].to(self.device).float())
             lab, codes = self.encode(xb)
             self._list[n0 + r0:n0 + r1] = lab
             self._codes[n0 + r0:n0 + r1] = codes
+            vr = slice(v0 + r0, v0 + r1) if fresh else vrows[r0:r1]
             if self.keep_vectors == "bf16":
-                self._vec[n0 + r0:n0 + r1] = self._pad(xb) if self.device.type == "cuda" else xb
+                self._vec[vr] = self._pad(xb) if self.device.type == "cuda" else xb
             elif self.keep_vectors == "fp8":
                 from ..ops.encoder_ops import quantize_fp8_rows
                 v = xb.to(torch.bfloat16) if self.device.type == "cuda" else xb
                 q8, sc = quantize_fp8_rows(v.contiguous())
-                self._vec[n0 + r0:n0 + r1] = q8
-                self._vscale[n0 + r0:n0 + r1] = sc
+                self._vec[vr] = q8
+                self._vscale[vr] = sc
             elif self.keep_vectors == "int8":
                 sc = xb.abs().amax(1).clamp_min(1e-30) / 127.0
                 q = torch.round(xb / sc[:, None]).clamp_(-127, 127).to(torch.int8)
-                self._vec[n0 + r0:n0 + r1] = q.view(torch.uint8)
-                self._vscale[n0 + r0:n0 + r1] = sc
+                self._vec[vr] = q.view(torch.uint8)
+                self._vscale[vr] = sc
         self.n = n0 + n
+        if fresh:
+            self.nv = v0 + n
+            self._nlive += n
         self._dirty = True
 
-    def _finalize(self, chunk: int = 1 << 24) -> None:
-        """Sort the code rows by list id (CSR) -- amortised over a batch of
-        adds; the codes are permuted in chunks into one new buffer, the
-        vectors never move (``pos`` follows the codes)."""
-        if not self._dirty:
+    # ------------------------------------------------------------------ maintain
+    def _flags(self, which: str) -> torch.Tensor:
+        f = getattr(self, which)
+        if f is None:
+            f = torch.zeros(max(self.cap, self.n, self.nv), dtype=torch.uint8, device=self.device)
+            setattr(self, which, f)
+        return f
+
+    def _lookup(self, ids: torch.Tensor, chunk: int = 1 << 24) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(vector rows, index into ``ids``) of the live vectors whose id is
+        in ``ids`` (int64 on the device, sorted, unique): one elementwise pass
+        over the ids column, a binary search per row in the small batch."""
+        rows, which = [], []
+        m = int(ids.numel())
+        for r0 in range(0, self.nv if m else 0, chunk):
+            r1 = min(self.nv, r0 + chunk)
+            v = self._vids[r0:r1]
+            j = torch.searchsorted(ids, v).clamp_(max=m - 1)
+            hit = ids[j] == v
+            if self._vdead is not None:
+                hit &= self._vdead[r0:r1] == 0
+            r = torch.nonzero(hit).flatten()
+            rows.append(r + r0)
+            which.append(j[r])
+        if not rows:
+            z = torch.zeros(0, dtype=torch.int64, device=self.device)
+            return z, z
+        return torch.cat(rows), torch.cat(which)
+
+    def remove(self, ids) -> int:
+        """Delete the vectors with these ids; ids the index does not hold (or
+        no longer holds) are ignored. Lazy: the rows are flagged here and leave
+        at the next search. Returns the number of vectors removed."""
+        ids = torch.unique(torch.as_tensor(ids, dtype=torch.int64).to(self.device).flatten())
+        rows, _ = self._lookup(ids)
+        k = int(rows.numel())
+        if k:
+            self._flags("_vdead")[rows] = 1
+            self._nlive -= k
+            self._dirty = True
+        return k
+
+    def upsert(self, ids, x: torch.Tensor) -> int:
+        """Insert or rewrite: a held id gets its vector re-encoded (its kept
+        copy is overwritten in its vector row, its old code row flagged, a new
+        code row appended to the tail), an id not held is appended as ``add``
+        would. Of a repeated id the last row counts. Returns the number of
+        ids that were already held."""
+        ids = torch.as_tensor(ids, dtype=torch.int64).to(self.device).flatten()
+        assert ids.numel() == x.shape[0]
+        if ids.numel() == 0:
+            return 0
+        uid, inv = torch.unique(ids, return_inverse=True)
+        last = torch.zeros(uid.numel(), dtype=torch.int64, device=self.device)
+        last.scatter_reduce_(0, inv, torch.arange(ids.numel(), device=self.device), "amax", include_self=False)
+        vrows, j = self._lookup(uid)
+        held = torch.zeros(uid.numel(), dtype=torch.bool, device=self.device)
+        held[j] = True
+        k = int(vrows.numel())
+        if k:
+            # the code rows (sorted part or tail) that point at these vectors leave
+            mark = torch.zeros(self.nv, dtype=torch.uint8, device=self.device)
+            mark[vrows] = 1
+            cd = self._flags("_cdead")
+            cd[: self.n] |= mark[self._pos[: self.n]]
+            del mark
+            self._append(x.to(self.device)[last[j]], None, vrows)
+        new = torch.nonzero(~held).flatten()
+        if new.numel():
+            self._append(x.to(self.device)[last[new]], uid[new], None)
+        return k
+
+    def translate_ids(self, table: torch.Tensor) -> None:
+        """Every live id ``i`` becomes ``table[i]``; a negative entry removes
+        the vector (a compaction of the caller's id space). ``table``: an
+        integer tensor on any device, indexed by the current ids."""
+        nv = self.nv
+        if nv == 0:
             return
-        n = self.n
+        t = torch.as_tensor(table).to(self.device, torch.int64).flatten()
+        if t.numel() == 0:
+            t = torch.full((1,), -1, dtype=torch.int64, device=self.device)
+        old = self._vids[:nv]
+        new = t[old.clamp(0, int(t.numel()) - 1)]
+        live = torch.ones(nv, dtype=torch.bool, device=self.device) if self._vdead is None else self._vdead[:nv] == 0
+        gone = live & ((new < 0) | (old < 0) | (old >= t.numel()))
+        self._vids[:nv] = torch.where(live & ~gone, new, old)
+        k = int(gone.sum())
+        if k:
+            self._flags("_vdead")[:nv] |= gone.to(torch.uint8)
+            self._nlive -= k
+            self._dirty = True
+
+    def _finalize_ref(self, chunk: int = 1 << 24) -> None:
+        """The torch formulation of :meth:`_finalize` (any device; the CPU
+        path and the oracle of the kernel path): the flagged rows are filtered
+        out, then the code rows are sorted by list id (CSR) with one stable
+        sort and permuted in chunks into one new buffer. The vector rows keep
+        their order (``pos`` follows the codes)."""
+        n, nv = self.n, self.nv
+        if self._cdead is not None or self._vdead is not None:
+            keep = torch.ones(n, dtype=torch.bool, device=self.device)
+            if self._cdead is not None:
+                keep &= self._cdead[:n] == 0
+            if self._vdead is not None:
+                keep &= self._vdead[self._pos[:n]] == 0
+                vkeep = self._vdead[:nv] == 0
+                vremap = torch.cumsum(vkeep, 0) - vkeep.long()
+                vi = torch.nonzero(vkeep).flatten()
+                nv = int(vi.numel())
+                for name in ("_vids", "_vec", "_vscale"):
+                    t = getattr(self, name)
+                    if t is not None:
+                        t[:nv] = t[vi]
+            ci = torch.nonzero(keep).flatten()
+            n = int(ci.numel())
+            self._codes[:n] = self._codes[ci]
+            self._list[:n] = self._list[ci]
+            p = self._pos[ci]
+            self._pos[:n] = vremap[p] if self._vdead is not None else p
+            self._cdead = self._vdead = None
+            self.n, self.nv = n, nv
         o = torch.argsort(self._list[:n], stable=True)
         codes = torch.empty_like(self._codes)
         for c0 in range(0, n, chunk):
@@ -253,16 +413,112 @@ class IVFPQIndex:
         cnt = torch.bincount(self._list[:n].long(), minlength=self.nlist)
         self.list_off = torch.zeros(self.nlist + 1, dtype=torch.int64, device=self.device)
         self.list_off[1:] = torch.cumsum(cnt, 0)
+        self._sorted_n = n
+        self._dirty = False
+
+    def _finalize(self, chunk_rows: Optional[int] = None) -> None:
+        """Bring the code rows back into CSR order -- amortised over a batch
+        of changes. On the GPU (``MAINT_KERNEL``), in place:
+
+        1. flags pending: one pass marks the surviving code rows and counts
+           them per list (ivfmaint.hip), the code columns and -- by the vector
+           flags -- the vector columns are compacted stably in place
+           (compact.hip), ``pos`` follows the vector rows;
+        2. a tail smaller than the sorted part: the tail alone is sorted by
+           list (O(tail)), the sorted part is spread upwards in place to open
+           a gap behind each list (ivfmaint.hip) and the tail rows drop in.
+
+        A first build, or a tail at least as large as the sorted part, takes
+        the full stable sort (:meth:`_finalize_ref`), which is also what the
+        CPU runs; both leave bit-identical arrays. ``chunk_rows``: rows per
+        chunk of the in-place moves (default ``self.chunk_rows``, else
+        ops.tenant_ops.rc_chunk_rows)."""
+        if not self._dirty:
+            return
+        if not (self.device.type == "cuda" and MAINT_KERNEL and self._sorted_n > 0):
+            return self._finalize_ref()
+        from ..ops import ivf_ops as V
+        from ..ops import tenant_ops as T
+        ch = int(chunk_rows or self.chunk_rows or T.rc_chunk_rows(self.m))
+        dev = self.device
+        st = self.last_maint = {"bytes_moved": 0, "direct": 0, "bounced": 0}  # of the wide in-place moves
+
+        def tally(r):
+            for k, v in zip(("bytes_moved", "direct", "bounced"), r):
+                st[k] += v
+        if self._cdead is not None or self._vdead is not None:
+            n, nv, s0 = self.n, self.nv, self._sorted_n
+            assert max(n, nv) < (1 << 31) - 1, "in-place maintenance indexes rows with int32"
+            vremap = None
+            if self._vdead is not None:
+                vkeep = (self._vdead[:nv] == 0).to(torch.uint8)
+                vremap = T.rc_remap_of(vkeep)
+            keep, cnt = V.ivf_mark_count(self._list[:n], self._pos, self._cdead, self._vdead, self.nlist, s0)
+            remap = T.rc_remap_of(keep)
+            z = torch.zeros((), dtype=torch.int64, device=dev)
+            # (argmin of 0 / 1 flags: the first dead row)
+            head = torch.stack([remap[n].long(), remap[s0].long(), keep.argmin(),
+                                vremap[nv].long() if vremap is not None else z,
+                                vkeep.argmin() if vremap is not None else z])
+            m, s1, first, mv, vfirst = (int(v) for v in head.cpu().tolist())
+            if vremap is not None and mv < nv:
+                wide = [t for t in (self._vec,) if t is not None]
+                for t in wide:
+                    rb = t.shape[1] * t.element_size()
+                    tally(T.rc_move_rows(t, vkeep, vremap, nv, vfirst, int(chunk_rows or self.chunk_rows
+                                                                            or T.rc_chunk_rows(rb))))
+                T.rc_move_scalars([t for t in (self._vids, self._vscale) if t is not None], vkeep, vremap, nv, mv)
+                self.nv = mv
+            if m < n:
+                tally(T.rc_move_rows(self._codes, keep, remap, n, first, ch))
+                T.rc_move_scalars([self._list, self._pos], keep, remap, n, m)
+            del keep, remap
+            if vremap is not None and mv < nv:
+                for c0 in range(0, m, 1 << 22):  # pos follows the vector rows
+                    c1 = min(m, c0 + (1 << 22))
+                    self._pos[c0:c1] = vremap[self._pos[c0:c1]]
+            self.list_off = torch.zeros(self.nlist + 1, dtype=torch.int64, device=dev)
+            self.list_off[1:] = torch.cumsum(cnt, 0)
+            self.n, self._sorted_n = m, s1
+            self._cdead = self._vdead = None
+        n, n0 = self.n, self._sorted_n
+        tail = n - n0
+        if tail and (n0 == 0 or tail >= n0):
+            return self._finalize_ref()
+        if tail:
+            t_codes, t_list, t_pos = self._codes[n0:n].clone(), self._list[n0:n].clone(), self._pos[n0:n].clone()
+            order, ins, dest = V.ivf_tail_slots(t_list, self.list_off, self.nlist)
+            first = int(self.list_off[int(t_list.min()) + 1])  # the rows of the lists behind the tail's first list
+            bounds = V.ivf_spread_bounds(self._list, ins, n0, first, ch)
+            bounce = torch.empty(min(ch, max(n0 - first, 0)) * self.m, dtype=torch.uint8, device=dev)
+            tally(V.ivf_spread_rows(self._codes, self._list, ins, n0, first, ch, bounds, bounce))
+            del bounce
+            # the narrow columns through the same kernel, no temporary of their
+            # own; the key column last, out of place from a copy of itself
+            nb = torch.empty(min(ch, max(n0 - first, 0)) * 8, dtype=torch.uint8, device=dev)
+            V.ivf_spread_rows(self._pos, self._list, ins, n0, first, ch, bounds, nb)
+            del nb
+            if first < n0:
+                key = self._list[:n0].clone()
+                V.ivf_spread_rows(self._list, key, ins, n0, first, ch, bounds, None, src=key)
+                del key
+            self._codes[dest] = t_codes[order]
+            self._list[dest] = t_list[order]
+            self._pos[dest] = t_pos[order]
+            self.list_off = self.list_off + ins
+        self._sorted_n = n
         self._dirty = False
 
     def __len__(self) -> int:
-        return int(self.n)
+        """The live vectors (removed ones leave at once, whatever is pending)."""
+        return int(self._nlive)
 
     def memory_bytes(self) -> int:
-        b = self.n * (self.m + 4 + 8 + 8)  # codes, list id, pos, id
+        n = self._nlive
+        b = n * (self.m + 4 + 8 + 8)  # codes, list id, pos, id
         if self._vec is not None:
-            b += self.n * self._vec.shape[1] * self._vec.element_size()
-        return b + (self.n * 4 if self._vscale is not None else 0)
+            b += n * self._vec.shape[1] * self._vec.element_size()
+        return b + (n * 4 if self._vscale is not None else 0)
 
     # ------------------------------------------------------------------ search
     def search(self, q: torch.Tensor, k: int = 10, nprobe: int = 16, rerank: int = 0):
