@@ -48,6 +48,7 @@ from ..engine.views import GraphBuffer, NodeView, ResultBatch, ShardView, Shards
 from ..models.graph import Edge, Node
 from . import providers as _providers
 from .consolidation import ConsolidationMixin
+from .filters import MemoryFilter
 from .interfaces import EmbeddingProvider, LLMProvider, Store
 from .memory_shard import MemoryShard
 from .profile import EMPTY_CONTEXT, Profile
@@ -343,7 +344,9 @@ class MemorySystem(ConsolidationMixin):
         fault_point("provider.llm")
         return self.llm.completion(messages, response_format)
 
-    def _search_batch(self, embs, k: int) -> List[List[str]]:
+    def _search_batch(self, embs, k: int, where=None) -> List[List[str]]:
+        if where is not None:
+            return self.vector_store.search_nodes_batch(embs, user_id=self.user_id, limit=k, where=where)
         fn = getattr(self.vector_store, "search_nodes_batch", None)
         if fn is not None:
             return fn(embs, user_id=self.user_id, limit=k)
@@ -606,21 +609,40 @@ class MemorySystem(ConsolidationMixin):
         kind = g.flags_of(out)[0]
         return [NodeView.of(g, x) for x, k in zip(out, kind) if k == NODE]
 
-    def search_memories(self, query: str, limit: int = 5) -> List[Node]:
+    def _where(self, where):
+        """``where`` of a search as a MemoryFilter (the predicate runs over the
+        bound tenant graph's HBM columns; a store that holds its own rows has none)."""
+        flt = MemoryFilter.coerce(where)
+        if flt is not None and not self._store_binds_graph():
+            raise NotImplementedError("a filtered search (where=) needs a store bound to the tenant graph (HBMStore)")
+        return flt
+
+    def search_memories(self, query: str, limit: int = 5, where=None) -> List[Node]:
+        """``where`` (a :class:`MemoryFilter` or a dict of its fields): only
+        the memories passing it are searched -- the ``limit`` nearest AMONG
+        them, not a post-filter of the nearest."""
+        if where is not None:
+            where = self._where(where)
         with tracer.stage("embed_query", self._device):
             q = self._get_embedding(query)
         with self._graph_lock:
             with tracer.stage("search", self._device):
-                ids = self.vector_store.search_nodes(q, user_id=self.user_id, limit=limit)
+                if where is None:
+                    ids = self.vector_store.search_nodes(q, user_id=self.user_id, limit=limit)
+                else:
+                    ids = self.vector_store.search_nodes(q, user_id=self.user_id, limit=limit, where=where)
             return [n for n in (self.buffer.get_node(i) for i in ids) if n is not None]
 
-    def search_memories_batch(self, queries: List[str], limit: int = 5) -> List[List[Node]]:
+    def search_memories_batch(self, queries: List[str], limit: int = 5, where=None) -> List[List[Node]]:
         """Batched ``search_memories`` (reference :1460-1472 per query): one
         embedding call (a device tensor when the encoder is on-device), one
         store search -- the fused MFMA candidate scan plus an fp32 re-rank
-        over the tenant's HBM rows -- and one row -> Node mapping."""
+        over the tenant's HBM rows -- and one row -> Node mapping. ``where``:
+        one filter for the whole batch (see :meth:`search_memories`)."""
+        if where is not None:
+            where = self._where(where)
         t0 = time.perf_counter()
-        out = self._search_finish(self._search_submit(queries, limit))
+        out = self._search_finish(self._search_submit(queries, limit, where))
         self._count_search(len(out), (time.perf_counter() - t0) * 1e3)
         return out
 
@@ -630,22 +652,24 @@ class MemorySystem(ConsolidationMixin):
         m["search_batches"] = m.get("search_batches", 0) + 1
         m["search_ms"] = m.get("search_ms", 0.0) + ms
 
-    def search_memories_stream(self, batches: Iterable[List[str]], limit: int = 5):
+    def search_memories_stream(self, batches: Iterable[List[str]], limit: int = 5, where=None):
         """Pipelined ``search_memories_batch`` for serving loops: batches i+1 ..
         i+STREAM_DEPTH are tokenised and their embed + scan enqueued on the
         device BEFORE the host waits for batch i and maps its rows to Nodes,
         so host work (tokenizer, result mapping) hides under device work.
         Yields one result list per input batch, in order; results equal
-        ``search_memories_batch``."""
+        ``search_memories_batch``. ``where``: one filter for all batches."""
+        if where is not None:
+            where = self._where(where)
         pending = collections.deque()
         for qs in batches:
-            pending.append(self._search_submit(qs, limit))
+            pending.append(self._search_submit(qs, limit, where))
             if len(pending) > STREAM_DEPTH:
                 yield self._search_finish(pending.popleft())
         while pending:
             yield self._search_finish(pending.popleft())
 
-    def _search_submit(self, queries, limit: int):
+    def _search_submit(self, queries, limit: int, where=None):
         """Enqueue embed + store search; returns a handle for _search_finish.
         With the graph-bound store the result rows stay on the device and come
         back with one async copy into pinned memory (no host sync here)."""
@@ -672,8 +696,12 @@ class MemorySystem(ConsolidationMixin):
                         # rows the graph does not hold as nodes are skipped (reference
                         # :1467-1472): marked on the device (by the re-rank kernel), so
                         # mapping needs no mirror
-                        _, rows = g.store_search(embs, int(limit), getattr(self.store, "metric", "l2"),
-                                                 node_rows=True)
+                        if where is None:
+                            _, rows = g.store_search(embs, int(limit), getattr(self.store, "metric", "l2"),
+                                                     node_rows=True)
+                        else:  # (every row a filtered search returns is a node)
+                            _, rows = g.store_search(embs, int(limit), getattr(self.store, "metric", "l2"),
+                                                     where=where)
                     if rows.is_cuda:
                         # the rows stay on the device until _search_finish copies them to
                         # pageable host memory on a stream that waits for THIS search only
@@ -684,7 +712,7 @@ class MemorySystem(ConsolidationMixin):
                         return ("rows_dev", g, rows, ev, g.row_epoch)
                     return ("rows", g, rows, None, g.row_epoch)
         with tracer.stage("search", self._device):
-            return ("ids", None, self._search_batch(embs, limit), None, 0)
+            return ("ids", None, self._search_batch(embs, limit, where), None, 0)
 
     def _search_finish(self, h) -> List[List[Node]]:
         kind_, g0, data, ev, epoch = h  # (the row epoch searched under: a compaction may run before the finish)
@@ -757,7 +785,9 @@ class MemorySystem(ConsolidationMixin):
         return {"device": str(self._device), "graph_rows": g.n, "hbm_graph_bytes": self._graph_bytes(),
                 "dead_rows": g.n - g.num_nodes(), "row_epoch": g.row_epoch,
                 "rows_reclaimed_total": g.rows_reclaimed_total, "ann_removed": g.ann_removed,
-                "ann_upserts": g.ann_upserts, "ann_rebuilds": g.ann_rebuilds, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
+                "ann_upserts": g.ann_upserts, "ann_rebuilds": g.ann_rebuilds,
+                "filtered_searches": g.filtered_searches, "filter_plans_built": g.filter_plans_built,
+                "filtered_sparse": g.filtered_sparse, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
                 "avg_search_batch_ms": round(sms / m["search_batches"], 3) if m.get("search_batches") else 0.0}
 
     def _graph_bytes(self) -> int:

@@ -96,12 +96,27 @@ async def consolidate():
     return {"status": _ms.run_consolidation()}
 
 
+def _csv(v: Optional[str]):
+    return [x for x in v.split(",") if x] if v is not None else None
+
+
 @app.get("/api/search")
-async def search(q: str, limit: int = 5):
+async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys: Optional[str] = None,
+                 min_salience: Optional[float] = None, max_salience: Optional[float] = None,
+                 since: Optional[float] = None, until: Optional[float] = None,
+                 accessed_since: Optional[float] = None, min_access_count: Optional[int] = None,
+                 super_nodes: Optional[bool] = None, exclude_ids: Optional[str] = None):
+    """``MemoryFilter`` fields as optional query parameters (the set-valued
+    ones comma separated); none given: the unfiltered search."""
     if not _ms:
         return []
-    return [{"id": n.id, "content": n.content, "salience": n.salience, "shard": n.shard_key}
-            for n in _ms.search_memories(q, limit=limit)]
+    where = {k: v for k, v in (("types", _csv(types)), ("shard_keys", _csv(shard_keys)),
+                               ("min_salience", min_salience), ("max_salience", max_salience), ("since", since),
+                               ("until", until), ("accessed_since", accessed_since),
+                               ("min_access_count", min_access_count), ("super_nodes", super_nodes),
+                               ("exclude_ids", _csv(exclude_ids))) if v is not None}
+    hits = _ms.search_memories(q, limit=limit, where=where) if where else _ms.search_memories(q, limit=limit)
+    return [{"id": n.id, "content": n.content, "salience": n.salience, "shard": n.shard_key} for n in hits]
 
 
 @app.get("/api/engine")

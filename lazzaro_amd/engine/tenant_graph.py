@@ -157,6 +157,26 @@ COS_FLOOR_SLACK = 0.01
 # buffer); COMPACT_KERNEL = False: the torch formulation the CPU runs
 # (col[:m] = col[keep_idx], a second copy of each column's kept rows)
 COMPACT_KERNEL = True
+# Filtered store search (store_search(..., where=)): a plan takes the indexed
+# scan (filter.hip gather_topk_kernel: reads the listed fp32 rows only, once
+# per tile of 8 queries) while passing rows x query tiles stays within this
+# many row reads; above it the dense masked scans run with the plan's bias.
+# Measured (bench/bench_filtered.py, 2,097,152 x 768 unit rows, L2, k = 10,
+# medians of 5 interleaved repetitions, profiles/r9/filtered_search/), indexed
+# against dense in ms:
+#   M = 1     630,145 rows 0.447 / 0.565   839,043 rows 0.577 / 0.572
+#   M = 64     42,156 rows 0.558 / 1.060   105,227 rows 1.253 / 1.122
+#   M = 1024   10,538 rows 1.432 / 2.147    21,061 rows 2.630 / 2.320
+# The largest list that still wins at M = 1 is 630,145 rows; 2^19 is the power
+# of two below it. The crossover does differ with M, and not only at 128
+# queries: at M = 64 it lies between 42k and 105k rows, so one row count for
+# every M < 128 would send a 420k-row list to a scan that takes 4.3 ms against
+# 1.24 ms. Counting the reads (rows x ceil(M / 8)) puts the limit at 65,536
+# rows for M = 64 and 4,096 for M = 1024, inside the measured win range of
+# each width. The dense time grows with the tenant, so on tenants well below
+# 2M rows this limit is generous and well above it conservative (not measured).
+FILTER_SPARSE_MAX_ROWS = 1 << 19
+FILTER_PLAN_CACHE = 8  # plans kept per graph (LRU); a plan holds 4 n bytes of bias + 4 bytes per listed row
 
 
 def _str_column(items=None):
@@ -303,6 +323,16 @@ class _BackgroundJob:
         if self._err is not None:
             raise self._err
         return self._out
+
+
+class FilterPlan:
+    """A filter evaluated over one tenant state: the per-row score bias
+    (store bias where the row passes, -inf elsewhere), the passing rows in
+    ascending order (int32, device) and their number."""
+    __slots__ = ("bias", "rows", "count")
+
+    def __init__(self, bias: torch.Tensor, rows: torch.Tensor, count: int):
+        self.bias, self.rows, self.count = bias, rows, count
 
 
 class TenantGraph:
@@ -702,6 +732,8 @@ class TenantGraph:
                     if kind_h is not None and r < len(kind_h) and kind_h[r] == NODE:
                         self._unlink_row(r)
                     self.content[r] = contents[j]
+                    if self.types[r] != t:
+                        self._type_rewritten(r)
                     self.types[r] = t
                 rl.append(r)
             self.n = r_next
@@ -1104,6 +1136,7 @@ class TenantGraph:
             return torch.cat(out)
 
     def set_scalar(self, r: int, name: str, value) -> None:
+        self._meta_gen += 1  # (no version bump here: cached filter plans key on this)
         col = getattr(self, name)
         with self.on_stream():
             col[r] = value
@@ -2413,14 +2446,20 @@ class TenantGraph:
         self._bias_cache[metric] = (self._store_version, b)
         return b
 
-    def store_search(self, Q: torch.Tensor, k: int, metric: str = "l2", node_rows: bool = False):
+    def store_search(self, Q: torch.Tensor, k: int, metric: str = "l2", node_rows: bool = False, where=None):
         """The store's vector search over this tenant (reference
         ``LanceDBStore.search_nodes``: flat scan, L2 unless told otherwise,
         vector_store.py:132-140). fp32 scores -- -|q-x|^2 for L2, cosine, or
         dot -- higher is closer; bf16 MFMA candidates are re-ranked in fp32.
         Returns (scores [M, k], rows [M, k]). ``node_rows``: rows that are not
         graph nodes come back as -1 (search_memories skips them, reference
-        memory_system.py:1467-1472) -- inside the re-rank kernel when it runs."""
+        memory_system.py:1467-1472) -- inside the re-rank kernel when it runs.
+        ``where`` (a ``core.filters.MemoryFilter`` or a dict of its fields):
+        only graph nodes in the store that pass it are searched (every result
+        row is a node, so ``node_rows`` changes nothing then)."""
+        if where is not None:
+            with self.on_stream():
+                return self._store_search_where(Q, k, metric, where)
         with self.on_stream():
             s, r = self._store_search(Q, k, metric, node_rows)
             if node_rows and not self._nodes_marked:
@@ -2430,7 +2469,161 @@ class TenantGraph:
 
     _nodes_marked = False  # the last _store_search already marked non-node rows (re-rank kernel)
 
-    def _store_search(self, Q, k, metric, node_rows=False):
+    # ---- filtered search: state (class defaults; the containers are made on first use)
+    _meta_gen = 0  # bumps on a scalar column write that bumps no other counter (set_scalar)
+    _tcode = None  # derived uint8 type-code column (device), rows [0, _tcode_n)
+    _tcode_n = 0
+    _tcode_epoch = -1
+    _tcode_dirty = None  # rows whose type was rewritten since the column was synced
+    type_code = None  # type name -> code, in order of first appearance
+    _filter_plans = None  # OrderedDict: plan key -> FilterPlan (LRU, FILTER_PLAN_CACHE entries)
+    filtered_searches = filter_plans_built = filtered_sparse = 0
+
+    def _type_rewritten(self, r: int) -> None:
+        """The type of row ``r`` changed: its code is re-written, and cached
+        plans dropped, at the next filtered search."""
+        self._meta_gen += 1
+        if self._tcode is not None:
+            if self._tcode_dirty is None:
+                self._tcode_dirty = []
+            self._tcode_dirty.append(int(r))
+
+    def _type_codes(self) -> torch.Tensor:
+        """The derived type-code column (uint8 per row, on the device; not a
+        NODE_COLS column, not persisted): built on the first filtered search
+        that tests types, extended for appended rows, re-written where a
+        type was rewritten, dropped by :meth:`compact`."""
+        n = self.n
+        if self.type_code is None:
+            self.type_code = {}
+        tc = self.type_code
+        if self._tcode is None or self._tcode_epoch != self.row_epoch or self._tcode_n > n:
+            self._tcode = torch.zeros(max(self.cap, n), dtype=torch.uint8, device=self.device)
+            self._tcode_n, self._tcode_epoch, self._tcode_dirty = 0, self.row_epoch, None
+        if self._tcode.numel() < n:
+            grown = torch.zeros(max(self.cap, n), dtype=torch.uint8, device=self.device)
+            grown[: self._tcode_n] = self._tcode[: self._tcode_n]
+            self._tcode = grown
+
+        def codes(names):
+            for t in names:
+                if t not in tc:
+                    if len(tc) >= 255:
+                        raise OverflowError("more than 255 distinct node types: the type filter's code column is uint8")
+                    tc[t] = len(tc)
+            return np.fromiter((tc[t] for t in names), dtype=np.uint8, count=len(names))
+
+        a = self._tcode_n
+        if a < n:
+            col = self.types
+            names = col.tolist()[a:n] if hasattr(col, "tolist") else list(col[a:n])
+            self._tcode[a:n] = torch.from_numpy(codes(names)).to(self.device)
+            self._tcode_n = n
+        if self._tcode_dirty:
+            rows = sorted(set(r for r in self._tcode_dirty if r < a))
+            if rows:
+                self._tcode[self._dev_rows(rows)] = torch.from_numpy(codes([self.types[r] for r in rows])).to(
+                    self.device)
+        self._tcode_dirty = None
+        return self._tcode
+
+    def _resolve_filter(self, flt):
+        """``flt`` (a MemoryFilter) against this tenant: type / shard names
+        to codes, excluded ids to rows (ops.filter_ops.Predicate)."""
+        from ..ops.filter_ops import Predicate
+        from .views import DEFAULT_SHARD
+        p = Predicate(min_sal=flt.min_salience, max_sal=flt.max_salience, since=flt.since, until=flt.until,
+                      accessed_since=flt.accessed_since, min_acc=flt.min_access_count,
+                      sup_mode=-1 if flt.super_nodes is None else int(flt.super_nodes))
+        if flt.types is not None:
+            self._type_codes()  # (every type the tenant holds has a code after this)
+            p.type_codes = sorted(self.type_code[t] for t in flt.types if t in self.type_code)
+        if flt.shard_keys is not None:
+            # a name the tenant never saw matches nothing; a row without a shard reads as the default shard
+            p.shard_codes = sorted(self.shard_code[s] for s in flt.shard_keys if s in self.shard_code)
+            p.neg_shard_pass = DEFAULT_SHARD in flt.shard_keys
+        if flt.exclude_ids is not None:
+            p.exclude_rows = sorted(self.row_of[i] for i in flt.exclude_ids if i in self.row_of)
+        return p
+
+    def _filter_plan(self, flt, l2: bool):
+        """The cached plan of ``flt`` for the metric's bias: (bias [n], rows
+        [count] ascending, count). Keyed by the filter, the metric and every
+        counter a write to a column the predicate reads bumps -- ``version``
+        (any graph mutation: inserts, touches, boosts, decay, merges, the
+        native applier), ``_store_version`` (stored / kind), ``row_epoch``
+        (compaction), ``n`` and ``_meta_gen`` (scalar writes through a node
+        view, type rewrites) -- so a plan is never served after a write it
+        could depend on. Building one reads ``count`` back (4 bytes): the
+        only host synchronisation of a filtered search."""
+        from collections import OrderedDict
+
+        from ..ops.filter_ops import PLAN_COLS, filter_plan
+        if self._filter_plans is None:
+            self._filter_plans = OrderedDict()
+        cache = self._filter_plans
+        now = (self.version, self._store_version, self.row_epoch, self.n, self._meta_gen)
+        if flt.types is not None:
+            self._type_codes()  # (may not change the counters; a rewritten type bumped _meta_gen already)
+        key = (flt.key(), bool(l2)) + now
+        plan = cache.get(key)
+        if plan is not None:
+            cache.move_to_end(key)
+            return plan
+        for old in [kk for kk in cache if kk[2:] != now]:  # plans no counter state can reach again
+            del cache[old]
+        pred = self._resolve_filter(flt)
+        n = self.n
+        bias, rows, count = filter_plan({c: getattr(self, c) for c in PLAN_COLS}, pred, self.sqn, n, l2,
+                                        self._tcode if pred.type_codes is not None else None)
+        c = int(count.cpu()[0])
+        rows = rows[:c].clone() if c < n // 2 else rows[:c]  # (a short list does not pin an n-row buffer)
+        plan = FilterPlan(bias, rows, c)
+        self.filter_plans_built += 1
+        cache[key] = plan
+        while len(cache) > FILTER_PLAN_CACHE:
+            cache.popitem(last=False)
+        return plan
+
+    def _store_search_where(self, Q, k, metric, where):
+        """:meth:`store_search` restricted to the rows passing ``where``.
+        Routes: no passing row -> all -1, no scan; on the GPU (L2, IP,
+        cosine over unit rows), while rows x query tiles stays within
+        FILTER_SPARSE_MAX_ROWS -> the indexed fp32 scan of the listed rows +
+        the exact re-rank (its result never consults ``_nodes_marked``: every
+        listed row is a node); otherwise the dense flow of
+        :meth:`_store_search` with the plan's bias as its row mask. A tenant
+        with an IVF-PQ index takes these flat routes too when filtered: the
+        index's candidate lists know nothing of the predicate, and masking
+        them afterwards would lose recall."""
+        from ..core.filters import MemoryFilter
+        flt = MemoryFilter.coerce(where)
+        n = self.n
+        dev = self.device
+        Qf = Q.to(dev, torch.float32)
+        if Qf.dim() == 1:
+            Qf = Qf[None, :]
+        M = Qf.shape[0]
+        self.filtered_searches += 1
+        if n == 0 or self.dim is None or Qf.shape[1] != self.dim:
+            return self._store_search(Qf, k, metric)
+        plan = self._filter_plan(flt, metric == "l2")
+        if plan.count == 0:
+            return (torch.full((M, k), NEG_INF, device=dev), torch.full((M, k), -1, dtype=torch.long, device=dev))
+        # (the indexed scan reads every listed row once per tile of 8 queries)
+        if self.on_gpu and plan.count * -(-M // 8) <= FILTER_SPARSE_MAX_ROWS and k <= CAND_SLOTS \
+                and (metric != "cosine" or self.unit_rows()):
+            from ..ops.filter_ops import gather_topk
+            self.filtered_sparse += 1
+            if metric == "cosine":
+                qn = Qf.norm(dim=1, keepdim=True)
+                Qf = Qf / torch.where(qn > 0, qn, torch.ones_like(qn))
+            _, cand = gather_topk(self.emb32, plan.rows, plan.count, Qf, CAND_SLOTS, plan.bias,
+                                  2.0 if metric == "l2" else 1.0)
+            return self._rerank_store(Qf, cand, k, metric, plan.bias)
+        return self._store_search(Qf, k, metric, False, plan)
+
+    def _store_search(self, Q, k, metric, node_rows=False, plan=None):
         from ..ops.search import flat_topk
         n = self.n
         dev = self.device
@@ -2443,10 +2636,10 @@ class TenantGraph:
         if metric == "cosine":
             qn = Qf.norm(dim=1, keepdim=True)
             Qf = Qf / torch.where(qn > 0, qn, torch.ones_like(qn))
-        bias = self.store_bias("l2" if metric == "l2" else "ip")
+        bias = self.store_bias("l2" if metric == "l2" else "ip") if plan is None else plan.bias
         alpha = 2.0 if metric == "l2" else 1.0
         cfg = self.ann_cfg
-        if cfg is not None and n >= cfg["min_rows"] and self.unit_rows():
+        if cfg is not None and plan is None and n >= cfg["min_rows"] and self.unit_rows():
             # IVF-PQ candidates (the store's index="ivfpq"), re-ranked exactly
             # in fp32 against this graph's rows with the store's row mask
             cand = self._ann_candidates(Qf, max(cfg.get("rerank", 1024), k), cfg)
@@ -2661,8 +2854,8 @@ class TenantGraph:
         o = torch.sort(s, dim=1, descending=True, stable=True).indices[:, :k]
         return self._pad_k(torch.gather(s, 1, o), torch.gather(cand, 1, o), k)
 
-    def search_ids(self, Q, k: int, metric: str = "l2") -> List[List[str]]:
-        _, r = self.store_search(Q, k, metric)
+    def search_ids(self, Q, k: int, metric: str = "l2", where=None) -> List[List[str]]:
+        _, r = self.store_search(Q, k, metric, where=where)
         ids = self.ids
         return [[ids[x] for x in row if x >= 0] for row in r.cpu().tolist()]
 
@@ -3048,6 +3241,8 @@ class TenantGraph:
         self._csr, self._csr_version = None, -1
         self._boost_state = T.BoostState()
         self._nodes_marked = False
+        self._tcode, self._tcode_n, self._tcode_dirty = None, 0, None  # rebuilt by the next type filter
+        self._filter_plans = None
         if shrink:
             cap = max(self._init_cap, math.ceil(1.1 * m))
             if cap != self.cap:

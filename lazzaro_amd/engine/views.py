@@ -124,6 +124,8 @@ class NodeView(Node):
 
     @type.setter
     def type(self, v: str) -> None:
+        if self._g.types[self._r] != v:
+            self._g._type_rewritten(self._r)
         self._g.types[self._r] = v
         self._g.set_scalar(self._r, "dirty", 1)
 

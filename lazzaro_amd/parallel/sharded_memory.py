@@ -570,13 +570,16 @@ class ShardedMemorySystem:
             out.append((s, meta))
         return out
 
-    def search_memories_batch(self, queries: Sequence[str], limit: int = 5) -> List[List[Dict]]:
+    def search_memories_batch(self, queries: Sequence[str], limit: int = 5, where=None) -> List[List[Dict]]:
         """Collective ``search_memories`` over the whole tenant (reference
         :1460-1472): every rank embeds its own queries, the query rows are
         all-gathered, each rank runs the store search (fused scan + fp32
         re-rank, L2) over its rows, the (score, owner, row) lists are merged
         (ties -> lower node number) and the winners' node dicts are returned
         to the rank that asked. Returns this rank's results."""
+        if where is not None:
+            raise NotImplementedError("ShardedMemorySystem.search_memories_batch takes no filter (where=)")
+
         g = self.g
         dev = self.device
         qs = list(queries)
