@@ -457,9 +457,10 @@ struct TileWalk {
   int next, end, step;
   __device__ __forceinline__ void init(int n_tiles) {
     const int G = gridDim.x, b = blockIdx.x;
-    const int x = b % 8, s = b / 8;
-    const int nb = (G - x + 7) / 8;          // blocks on this XCD
-    const int per = (n_tiles + 7) / 8;       // tiles per XCD share
+    const int nx = min(G, 8);                // shares: a grid under 8 blocks (a CU budget) has fewer
+    const int x = b % nx, s = b / nx;
+    const int nb = (G - x + nx - 1) / nx;    // blocks on this XCD
+    const int per = (n_tiles + nx - 1) / nx;  // tiles per XCD share
     const int lo = min(x * per, n_tiles);
     end = min(lo + per, n_tiles);
     next = lo + s;

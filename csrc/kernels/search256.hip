@@ -134,6 +134,15 @@ struct BlkCands {
   const float* qs = nullptr;
 };
 
+// Score of the int8 scan, one rounding per step whatever the surrounding code
+// lets the compiler contract: p = float(sum) * row scale (the int32 -> float
+// conversion is exact, |sum| < 2^24 for D <= 1024), score = fma(al, p, bias)
+// with al = alpha * query scale. Every int8 epilogue (OPT 24, the tiered
+// prefilter of OPT bit 6, the dual scan) takes its scores from these two, so
+// the schedules append bit-identical records.
+__device__ __forceinline__ float i8_prod(int v, float rs) { return __fmul_rn((float)v, rs); }
+__device__ __forceinline__ float i8_score(float al, float p, float b) { return __fmaf_rn(al, p, b); }
+
 // DUAL: one GEMM pass serves two searches of the same queries -- list A keeps
 // every row with score >= thr[q] (no label filter), list B keeps rows whose
 // label equals the query's and score >= thr2[q]. Consolidation needs exactly
@@ -270,12 +279,14 @@ __global__ __launch_bounds__(NT, 1) void flat_cand_persistent_kernel(
         // int8 scan: the query's scale (slot 6) joins alpha
         al[j] = MMA::kInt ? alpha * e_thr[6 * 256 + qlo] : alpha;
       }
-      if constexpr (MMA::kInt) {
+      typedef int i32x4 __attribute__((ext_vector_type(4)));
+      const float* e_rs = e_thr + 5 * 256;
+      // OPT bit 6 (int8 only): tiered prefilter on the raw int32 sums, below
+      constexpr bool TIER = MMA::kInt && (OPT & 64) != 0;
+      if constexpr (MMA::kInt && !TIER) {
         // int32 sums -> float * the row's scale (slot 5), in place: the
         // rest of the epilogue (column prefilter, per-score test) is the bf16
         // one with alpha = alpha * qscale. Exact: |acc| < 2^24 for D <= 1024.
-        typedef int i32x4 __attribute__((ext_vector_type(4)));
-        const float* e_rs = e_thr + 5 * 256;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
           const f32x4 rs = *reinterpret_cast<const f32x4*>(e_rs + wr * 128 + i * 16 + 4 * (lane >> 4));
@@ -283,16 +294,43 @@ __global__ __launch_bounds__(NT, 1) void flat_cand_persistent_kernel(
           for (int j = 0; j < 4; ++j) {
             const i32x4 v = __builtin_bit_cast(i32x4, acc[i][j]);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) acc[i][j][e] = (float)v[e] * rs[e];
+            for (int e = 0; e < 4; ++e) acc[i][j][e] = i8_prod(v[e], rs[e]);
           }
         }
       }
       const bool full = r0 + BM <= nrows;
-      // (int8: a prefilter on the raw int32 sums, bounded by the wave's
-      // largest / smallest row scale and converting only surviving columns,
-      // measured 9.8 vs 8.9 ms per headline store search -- the looser bound
-      // lets more waves into the per-score path, which then also pays the
-      // conversion: profiles/r6/serving/i8_int_prefilter_ab/)
+      // OPT bit 6: the sums stay int32. A quad is the 4 rows a lane holds in
+      // one accumulator register group; with R = the largest of its 4 row
+      // scales, B = the largest of its 4 biases and m = max(its 4 sums, 0),
+      //   u = fma(al, float(m) * R, B) >= every score of the quad for al > 0:
+      // float(v) * rs <= float(m) * R in exact arithmetic for any sign of v
+      // (m >= 0, 0 <= rs <= R), and the two roundings are those of the score
+      // (i8_prod / i8_score), which are monotone. u costs 5 VALU per quad
+      // (2 v_max3_i32, cvt, mul, fma) against 12 for four scores, is only as
+      // loose as the spread of 4 neighbouring row scales, and what it lets
+      // through pays for one quad, not for a column. (A bound by the WAVE's
+      // largest row scale measured 9.8 vs 8.9 ms per headline store search:
+      // thresholds sit ~4-5 sigma out, so a bound 15 % loose passes ~20x as
+      // often, and each pass paid the whole column:
+      // profiles/r6/serving/i8_int_prefilter_ab/.) On random unit rows (scales
+      // ~8 % apart inside a quad) ~9 quads pass per candidate, so the per-score
+      // part costs what it did and the gain is the conversion part:
+      // profiles/r10/scan_prefilter/. Lanes with al <= 0 (a zero query) take
+      // no shortcut.
+      [[maybe_unused]] float qR[8], qB[8];
+      if constexpr (TIER) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int rl = wr * 128 + i * 16 + 4 * (lane >> 4);
+          const f32x4 rs = *reinterpret_cast<const f32x4*>(e_rs + rl);
+          qR[i] = fmaxf(fmaxf(fmaxf(rs[0], rs[1]), rs[2]), rs[3]);
+          qB[i] = 0.f;
+          if constexpr (HAS_BIAS) {
+            const f32x4 bv = *reinterpret_cast<const f32x4*>(e_bias + rl);
+            qB[i] = fmaxf(fmaxf(fmaxf(bv[0], bv[1]), bv[2]), bv[3]);
+          }
+        }
+      }
       // OPT bit 4: column prefilter. For alpha > 0 every score of query
       // column j is <= alpha * max_i acc[i][j] + max(bias over the wave's
       // rows), so a column whose bound is below its threshold (the common
@@ -300,11 +338,28 @@ __global__ __launch_bounds__(NT, 1) void flat_cand_persistent_kernel(
       // VALU per tile instead of ~320. Labels only remove rows, and list B's
       // threshold is covered by min(th, th2), so the bound is conservative.
       float bmax = 0.f;
-      if constexpr ((OPT & 16) != 0 && HAS_BIAS)
+      if constexpr ((OPT & 16) != 0 && HAS_BIAS && !TIER)
         bmax = wave_max(fmaxf(e_bias[wr * 128 + lane], e_bias[wr * 128 + 64 + lane]));
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        if constexpr ((OPT & 16) != 0) {
+        [[maybe_unused]] float qu[8];
+        [[maybe_unused]] float tcut = 0.f;
+        [[maybe_unused]] bool tier_on = false;
+        if constexpr (TIER) {
+          float cm = LZK_NEG_INF;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const i32x4 v = __builtin_bit_cast(i32x4, acc[i][j]);
+            const int m = max(max(max(v[0], v[1]), v[2]), max(v[3], 0));
+            qu[i] = i8_score(al[j], i8_prod(m, qR[i]), qB[i]);
+            cm = fmaxf(cm, qu[i]);
+          }
+          const float tmin = DUAL ? fminf(th[j], th2[j]) : th[j];
+          // the column test's slack and shape: +inf -> NaN -> skipped, -inf -> kept
+          tcut = tmin - 1e-6f * fabsf(tmin);
+          tier_on = al[j] > 0.f;
+          if (tier_on && !(cm >= tcut)) continue;
+        } else if constexpr ((OPT & 16) != 0) {
           float mx = acc[0][j][0];
 #pragma unroll
           for (int i = 0; i < 8; ++i)
@@ -319,13 +374,21 @@ __global__ __launch_bounds__(NT, 1) void flat_cand_persistent_kernel(
         for (int i = 0; i < 8; ++i) {
           const int rl = wr * 128 + i * 16 + 4 * (lane >> 4);
           const int rb = r0 + rl;
+          if constexpr (TIER) {  // only the quads whose own bound clears the threshold
+            if (tier_on && !(qu[i] >= tcut)) continue;
+          }
           f32x4 bv = {0.f, 0.f, 0.f, 0.f};
           if (HAS_BIAS) bv = *reinterpret_cast<const f32x4*>(e_bias + rl);
+          [[maybe_unused]] f32x4 rs = {0.f, 0.f, 0.f, 0.f};
+          if constexpr (TIER) rs = *reinterpret_cast<const f32x4*>(e_rs + rl);
           float sc[4];
           float m = LZK_NEG_INF;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            sc[e] = al[j] * acc[i][j][e] + bv[e];
+            if constexpr (TIER)
+              sc[e] = i8_score(al[j], i8_prod(__builtin_bit_cast(i32x4, acc[i][j])[e], rs[e]), bv[e]);
+            else if constexpr (MMA::kInt) sc[e] = i8_score(al[j], acc[i][j][e], bv[e]);
+            else sc[e] = al[j] * acc[i][j][e] + bv[e];
             const bool in = full || (rb + e < nrows);
             if (!in) sc[e] = LZK_NEG_INF;
             if constexpr (HAS_LABEL && !DUAL) {  // single search: the label filters list A
@@ -444,6 +507,12 @@ int g_cand_persist = -1;
 // +prefilter 13.38, both 12.80 ms (-6.8 %); cross-tile prefetch (bit 5) was
 // 8 % slower and stays an A/B knob only.
 constexpr int kCandOpt = 24;
+// The int8 store scan (lzk_flat_cand_i8): kCandOpt | 64 = the tiered prefilter
+// on the int32 sums (bit 6) instead of the float one. Both append the same
+// records; interleaved on 10M x 768 x 1024 queries the store search takes 8.25
+// against 8.41 ms, the raw scan 6.99 against 7.15 ms
+// (profiles/r10/scan_prefilter/).
+constexpr int kI8Opt = kCandOpt | 64;
 // The dual kernel's list-B threshold comes from a 1/S sample of one shard's
 // rows, so it is low and the column prefilter rarely skips
 // (profiles/ab_dual_r1.json) 0: 16.27 ms, body2: 15.65, +prefilter 15.90.
@@ -1589,14 +1658,18 @@ LZK_EXPORT int lzk_flat_cand_i8(const void* X8, long ldx_bytes, int nrows, const
   } while (0)
   // (a cross-tile prefetch variant, OPT bit 5, measured 11.0 vs 10.0 ms per
   // store search on 10M x 768 x 1024 -- bench/ab_i8_search.py -- and spills)
-  // g_i8_opt (probe A/B only, lzk_set_i8_opt): 28 = the GEMM without the
-  // candidate epilogue (OPT bit 2), 8 = no column prefilter
+  // g_i8_opt (lzk_set_i8_opt; A/B and probes): 24 = the float column
+  // prefilter (every sum converted first), 88 = the tiered prefilter on the
+  // int32 sums (OPT bit 6), 28 = the GEMM without the candidate epilogue
+  // (OPT bit 2), 8 = no column prefilter; anything else: kI8Opt
 #define LZK_GIS(B)                              \
   do {                                          \
     switch (g_i8_opt) {                         \
       case 28: LZK_GIO(B, 28); break;           \
       case 8: LZK_GIO(B, 8); break;             \
-      default: LZK_GIO(B, kCandOpt); break;     \
+      case 24: LZK_GIO(B, 24); break;           \
+      case 88: LZK_GIO(B, 88); break;           \
+      default: LZK_GIO(B, kI8Opt); break;       \
     }                                           \
   } while (0)
   if (bias) LZK_GIS(true);
