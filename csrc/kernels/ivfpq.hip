@@ -12,6 +12,9 @@
 //     rows (16-byte code loads, LDS gathers) into a register top-K, then the
 //     256 per-thread lists are reduced by wave argmax rounds + one 4-way merge;
 //   * partial lists go through the shared topk_merge kernel (search.hip).
+// The kernel-level oracle of the four query kernels below (fp64, bit-exact on
+// integer-grid inputs, ties by (score desc, row asc)) is
+// tests/kernels/_ivfpq_ref.py, used by tests/kernels/test_ivfpq_scan_gpu.py.
 #include "lzk_common.h"
 
 namespace {

@@ -543,7 +543,7 @@ class IVFPQIndex:
             s, rows = self._scan_deep(probes.to(torch.int32).contiguous(), coarse.contiguous(), lut, kk)
         if rerank and self._vec is not None:
             vrows = torch.where(rows >= 0, self._pos[rows.clamp_min(0)], torch.full_like(rows, -1))
-            if self._rerank_gpu_ok(k):
+            if self._rerank_gpu_ok(k) and self._rerank_fits(vrows.shape[1]):
                 s, vr = self._rerank_gpu(qf, vrows.contiguous(), k)
             else:
                 valid = vrows >= 0
@@ -588,6 +588,15 @@ class IVFPQIndex:
         w = self._vec.shape[1]
         row_bytes = w if self._vscale is not None else 2 * w
         return row_bytes % 256 == 0
+
+    # rerank_kernel keeps the fp32 query and one fp32 score per candidate in
+    # LDS; lzk_rerank refuses more than the CU's 160 KiB
+    RERANK_LDS = 160 * 1024
+
+    def _rerank_fits(self, R: int) -> bool:
+        """Whether a candidate depth of ``R`` fits the fused re-rank; a deeper
+        one goes through the library path of :meth:`search`."""
+        return (self._vec.shape[1] + R) * 4 <= self.RERANK_LDS
 
     def _rerank_gpu(self, qf: torch.Tensor, rows: torch.Tensor, k: int):
         """Fused exact re-rank over the kept copy (csrc/kernels/ivfpq.hip
