@@ -112,7 +112,7 @@ def step_ab(a):
         wins = [r["count"] for r in out["table"] if r["M"] == M and r["sparse"]["median_ms"] < r["dense"]["median_ms"]]
         out[f"largest_count_sparse_wins_M{M}"] = max(wins) if wins else 0
     out["counters"] = {"filtered_searches": g.filtered_searches, "filter_plans_built": g.filter_plans_built,
-                       "filtered_sparse": g.filtered_sparse}
+                       "filtered_sparse": g.filtered_sparse, "filtered_ann": g.filtered_ann}
     return out
 
 

@@ -64,9 +64,16 @@ struct LaneTopK {
   }
 };
 
-template <int K, int M>
+// IDX (the filtered scans, lzk_ivfpq_*_f): list_off holds offsets into frows --
+// the code rows that pass a filter, ascending (lzk_ivfpq_filter_rows) -- and a
+// step reads its code row through frows. Positions of the compacted list take
+// the place of rows everywhere but in the code address and the reported row,
+// so a lane still sees ascending rows. A block whose filtered list is empty
+// writes its padding and leaves before it stages the LUT.
+template <int K, int M, bool IDX>
 __global__ __launch_bounds__(256) void ivfpq_scan_kernel(const unsigned char* __restrict__ codes,
                                                          const long* __restrict__ list_off,
+                                                         const int* __restrict__ frows,
                                                          const int* __restrict__ probes,
                                                          const float* __restrict__ coarse,
                                                          const float* __restrict__ lut, int nprobe,
@@ -77,6 +84,15 @@ __global__ __launch_bounds__(256) void ivfpq_scan_kernel(const unsigned char* __
   const int qp = blockIdx.x;  // query * nprobe + p
   const int q = qp / nprobe;
   const int list = probes[qp];
+  if constexpr (IDX) {
+    if (list < 0 || list_off[list] == list_off[list + 1]) {  // (block-uniform)
+      if (threadIdx.x < K) {
+        out_s[(long)qp * K + threadIdx.x] = LZK_NEG_INF;
+        out_i[(long)qp * K + threadIdx.x] = -1;
+      }
+      return;
+    }
+  }
   const float base = coarse[qp];
   const float* L = lut + (long)q * M * 256;
   for (int t = threadIdx.x * 4; t < M * 256; t += 256 * 4)
@@ -85,7 +101,9 @@ __global__ __launch_bounds__(256) void ivfpq_scan_kernel(const unsigned char* __
   LaneTopK<K> top;
   top.init();
   const long r0 = (list >= 0) ? list_off[list] : 0, r1 = (list >= 0) ? list_off[list + 1] : 0;
-  for (long r = r0 + threadIdx.x; r < r1; r += 256) {
+  for (long i = r0 + threadIdx.x; i < r1; i += 256) {
+    long r = i;
+    if constexpr (IDX) r = frows[i];
     const unsigned char* c = codes + r * M;
     const float s = pq_score<M>(c, slut, base);
     top.push(s, (int)r);
@@ -138,9 +156,11 @@ __global__ __launch_bounds__(256) void ivfpq_scan_kernel(const unsigned char* __
 // neighbours in few lists (a list can hold thousands of one cluster's rows, so
 // the depth is 4 x 128). out[(qp * 4 + wave) * DEEP_W + j]; rows -1 = none.
 constexpr int DEEP_W = 128;
-template <int M>
+// IDX: a thread owns positions f0 + t, f0 + t + 256, ... of the filtered list.
+template <int M, bool IDX>
 __global__ __launch_bounds__(256) void ivfpq_scan_deep_kernel(const unsigned char* __restrict__ codes,
                                                               const long* __restrict__ list_off,
+                                                              const int* __restrict__ frows,
                                                               const int* __restrict__ probes,
                                                               const float* __restrict__ coarse,
                                                               const float* __restrict__ lut, int nprobe,
@@ -149,6 +169,15 @@ __global__ __launch_bounds__(256) void ivfpq_scan_deep_kernel(const unsigned cha
   const int qp = blockIdx.x;
   const int q = qp / nprobe;
   const int list = probes[qp];
+  if constexpr (IDX) {
+    if (list < 0 || list_off[list] == list_off[list + 1]) {  // (block-uniform)
+      for (int j = threadIdx.x; j < 4 * DEEP_W; j += 256) {
+        out_s[(long)qp * 4 * DEEP_W + j] = LZK_NEG_INF;
+        out_i[(long)qp * 4 * DEEP_W + j] = -1;
+      }
+      return;
+    }
+  }
   const float base = coarse[qp];
   const float* L = lut + (long)q * M * 256;
   for (int t = threadIdx.x * 4; t < M * 256; t += 256 * 4)
@@ -157,7 +186,9 @@ __global__ __launch_bounds__(256) void ivfpq_scan_deep_kernel(const unsigned cha
   LaneTopK<16> top;
   top.init();
   const long r0 = (list >= 0) ? list_off[list] : 0, r1 = (list >= 0) ? list_off[list + 1] : 0;
-  for (long r = r0 + threadIdx.x; r < r1; r += 256) {
+  for (long i = r0 + threadIdx.x; i < r1; i += 256) {
+    long r = i;
+    if constexpr (IDX) r = frows[i];
     const unsigned char* c = codes + r * M;
     const float s = pq_score<M>(c, slut, base);
     top.push(s, (int)r);
@@ -174,6 +205,16 @@ __global__ __launch_bounds__(256) void ivfpq_scan_deep_kernel(const unsigned cha
       const float s2 = __shfl_xor(bs, off, 64);
       const int i2 = __shfl_xor(bi, off, 64);
       if (better(s2, i2, bs, bi)) { bs = s2; bi = i2; }
+    }
+    if constexpr (IDX) {
+      // a filtered list often leaves a wave a handful of rows: once its lanes
+      // are drained (bi is wave-uniform) the rest is padding, written at once
+      // -- a round is a dozen dependent cross-lane steps, DEEP_W of them were
+      // most of the kernel's time on short lists
+      if (bi == 0x7fffffff) {
+        for (int jj = j + lane; jj < DEEP_W; jj += 64) { out_s[o + jj] = LZK_NEG_INF; out_i[o + jj] = -1; }
+        break;
+      }
     }
     if (lane == 0) {
       const bool none = bi == 0x7fffffff || bs == LZK_NEG_INF;
@@ -196,9 +237,12 @@ __global__ __launch_bounds__(256) void ivfpq_scan_deep_kernel(const unsigned cha
 // query's neighbours concentrate in one list (the per-list pools cap at
 // 4 x DEEP_W). Appends are wave-aggregated (ballot + one atomicAdd per wave
 // per step); cnt[q] keeps counting past cap so the caller sees an overflow.
-template <int M>
+// IDX: the trip count is that of the filtered list (still uniform), cnt[q]
+// counts passing rows only.
+template <int M, bool IDX>
 __global__ __launch_bounds__(256) void ivfpq_scan_thresh_kernel(const unsigned char* __restrict__ codes,
                                                                 const long* __restrict__ list_off,
+                                                                const int* __restrict__ frows,
                                                                 const int* __restrict__ probes,
                                                                 const float* __restrict__ coarse,
                                                                 const float* __restrict__ lut,
@@ -209,6 +253,9 @@ __global__ __launch_bounds__(256) void ivfpq_scan_thresh_kernel(const unsigned c
   const int qp = blockIdx.x;
   const int q = qp / nprobe;
   const int list = probes[qp];
+  if constexpr (IDX) {
+    if (list < 0 || list_off[list] == list_off[list + 1]) return;  // (block-uniform)
+  }
   const float base = coarse[qp];
   const float t = thr[q];
   const float* L = lut + (long)q * M * 256;
@@ -218,13 +265,15 @@ __global__ __launch_bounds__(256) void ivfpq_scan_thresh_kernel(const unsigned c
   const int lane = threadIdx.x & 63;
   const long r0 = (list >= 0) ? list_off[list] : 0, r1 = (list >= 0) ? list_off[list + 1] : 0;
   for (long rb = r0; rb < r1; rb += 256) {  // uniform trip count: every lane reaches the ballot
-    const long r = rb + threadIdx.x;
+    const long i = rb + threadIdx.x;
+    long r = i;
     float s = LZK_NEG_INF;
-    if (r < r1) {
+    if (i < r1) {
+      if constexpr (IDX) r = frows[i];
       const unsigned char* c = codes + r * M;
       s = pq_score<M>(c, slut, base);
     }
-    const bool take = r < r1 && s >= t;
+    const bool take = i < r1 && s >= t;
     const unsigned long long m = __ballot(take);
     if (m == 0ull) continue;
     const int leader = __ffsll((long long)m) - 1;
@@ -363,37 +412,55 @@ __global__ __launch_bounds__(256) void rerank_kernel(const unsigned char* __rest
   }
 }
 
-template <int K>
-hipError_t launch_scan(int M, const unsigned char* codes, const long* off, const int* probes, const float* coarse,
-                       const float* lut, int nq, int nprobe, float* os, int* oi, hipStream_t st) {
+#define LZK_PQ_M_SWITCH(M, BAD)                                                                                    \
+  switch (M) {                                                                                                      \
+    case 8: GO(8); break;                                                                                           \
+    case 16: GO(16); break;                                                                                         \
+    case 32: GO(32); break;                                                                                         \
+    case 48: GO(48); break;                                                                                         \
+    case 64: GO(64); break;                                                                                         \
+    case 96: GO(96); break;                                                                                         \
+    case 128: GO(128); break;                                                                                       \
+    default: return BAD;                                                                                            \
+  }
+
+template <int K, bool IDX>
+hipError_t launch_scan(int M, const unsigned char* codes, const long* off, const int* frows, const int* probes,
+                       const float* coarse, const float* lut, int nq, int nprobe, float* os, int* oi,
+                       hipStream_t st) {
   dim3 grid(nq * nprobe), block(256);
   size_t lds = (size_t)M * 256 * sizeof(float);
 #define GO(MM)                                                                                                      \
   do {                                                                                                              \
-    (void)hipFuncSetAttribute((const void*)ivfpq_scan_kernel<K, MM>, hipFuncAttributeMaxDynamicSharedMemorySize,   \
-                              (int)lds);                                                                            \
-    hipLaunchKernelGGL((ivfpq_scan_kernel<K, MM>), grid, block, lds, st, codes, off, probes, coarse, lut, nprobe,  \
-                       os, oi);                                                                                     \
+    (void)hipFuncSetAttribute((const void*)ivfpq_scan_kernel<K, MM, IDX>,                                           \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
+    hipLaunchKernelGGL((ivfpq_scan_kernel<K, MM, IDX>), grid, block, lds, st, codes, off, frows, probes, coarse,   \
+                       lut, nprobe, os, oi);                                                                        \
   } while (0)
-  switch (M) {
-    case 8: GO(8); break;
-    case 16: GO(16); break;
-    case 32: GO(32); break;
-    case 48: GO(48); break;
-    case 64: GO(64); break;
-    case 96: GO(96); break;
-    case 128: GO(128); break;
-    default: return hipErrorInvalidValue;
-  }
+  LZK_PQ_M_SWITCH(M, hipErrorInvalidValue)
 #undef GO
   return hipGetLastError();
 }
 
-}  // namespace
+template <bool IDX>
+int scan_any(const void* codes, const long* off, const int* frows, const int* probes, const float* coarse,
+             const float* lut, int nq, int nprobe, int M, int kslot, float* os, int* oi, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned char* c = (const unsigned char*)codes;
+  hipError_t e;
+  switch (kslot) {
+    case 1: e = launch_scan<1, IDX>(M, c, off, frows, probes, coarse, lut, nq, nprobe, os, oi, st); break;
+    case 4: e = launch_scan<4, IDX>(M, c, off, frows, probes, coarse, lut, nq, nprobe, os, oi, st); break;
+    case 10: e = launch_scan<10, IDX>(M, c, off, frows, probes, coarse, lut, nq, nprobe, os, oi, st); break;
+    case 16: e = launch_scan<16, IDX>(M, c, off, frows, probes, coarse, lut, nq, nprobe, os, oi, st); break;
+    default: return (int)hipErrorInvalidValue;
+  }
+  return (int)e;
+}
 
-// deep candidates: [nq, nprobe, 4 * DEEP_W] (score, code row; -1 = empty)
-LZK_EXPORT int lzk_ivfpq_scan_deep(const void* codes, const long* list_off, const int* probes, const float* coarse,
-                                   const float* lut, int nq, int nprobe, int M, float* os, int* oi, void* stream) {
+template <bool IDX>
+int deep_any(const void* codes, const long* off, const int* frows, const int* probes, const float* coarse,
+             const float* lut, int nq, int nprobe, int M, float* os, int* oi, void* stream) {
   if (nq <= 0 || nprobe <= 0) return (int)hipErrorInvalidValue;
   dim3 grid((unsigned)nq * nprobe), block(256);
   size_t lds = (size_t)M * 256 * sizeof(float);
@@ -401,23 +468,45 @@ LZK_EXPORT int lzk_ivfpq_scan_deep(const void* codes, const long* list_off, cons
   const unsigned char* c = (const unsigned char*)codes;
 #define GO(MM)                                                                                                      \
   do {                                                                                                              \
-    (void)hipFuncSetAttribute((const void*)ivfpq_scan_deep_kernel<MM>,                                              \
+    (void)hipFuncSetAttribute((const void*)ivfpq_scan_deep_kernel<MM, IDX>,                                         \
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
-    hipLaunchKernelGGL((ivfpq_scan_deep_kernel<MM>), grid, block, lds, st, c, list_off, probes, coarse, lut,       \
-                       nprobe, os, oi);                                                                             \
+    hipLaunchKernelGGL((ivfpq_scan_deep_kernel<MM, IDX>), grid, block, lds, st, c, off, frows, probes, coarse,     \
+                       lut, nprobe, os, oi);                                                                        \
   } while (0)
-  switch (M) {
-    case 8: GO(8); break;
-    case 16: GO(16); break;
-    case 32: GO(32); break;
-    case 48: GO(48); break;
-    case 64: GO(64); break;
-    case 96: GO(96); break;
-    case 128: GO(128); break;
-    default: return (int)hipErrorInvalidValue;
-  }
+  LZK_PQ_M_SWITCH(M, (int)hipErrorInvalidValue)
 #undef GO
   return (int)hipGetLastError();
+}
+
+template <bool IDX>
+int thresh_any(const void* codes, const long* off, const int* frows, const int* probes, const float* coarse,
+               const float* lut, const float* thr, int nq, int nprobe, int M, int cap, int* cnt, float* os, int* oi,
+               void* stream) {
+  if (nq <= 0 || nprobe <= 0 || cap <= 0) return (int)hipErrorInvalidValue;
+  dim3 grid((unsigned)nq * nprobe), block(256);
+  size_t lds = (size_t)M * 256 * sizeof(float);
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned char* c = (const unsigned char*)codes;
+#define GO(MM)                                                                                                      \
+  do {                                                                                                              \
+    (void)hipFuncSetAttribute((const void*)ivfpq_scan_thresh_kernel<MM, IDX>,                                       \
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
+    hipLaunchKernelGGL((ivfpq_scan_thresh_kernel<MM, IDX>), grid, block, lds, st, c, off, frows, probes, coarse,   \
+                       lut, thr, nprobe, cap, cnt, os, oi);                                                         \
+  } while (0)
+  LZK_PQ_M_SWITCH(M, (int)hipErrorInvalidValue)
+#undef GO
+  return (int)hipGetLastError();
+}
+
+#undef LZK_PQ_M_SWITCH
+
+}  // namespace
+
+// deep candidates: [nq, nprobe, 4 * DEEP_W] (score, code row; -1 = empty)
+LZK_EXPORT int lzk_ivfpq_scan_deep(const void* codes, const long* list_off, const int* probes, const float* coarse,
+                                   const float* lut, int nq, int nprobe, int M, float* os, int* oi, void* stream) {
+  return deep_any<false>(codes, list_off, nullptr, probes, coarse, lut, nq, nprobe, M, os, oi, stream);
 }
 
 LZK_EXPORT int lzk_ivfpq_deep_width() { return 4 * DEEP_W; }
@@ -426,47 +515,39 @@ LZK_EXPORT int lzk_ivfpq_deep_width() { return 4 * DEEP_W; }
 LZK_EXPORT int lzk_ivfpq_scan_thresh(const void* codes, const long* list_off, const int* probes, const float* coarse,
                                      const float* lut, const float* thr, int nq, int nprobe, int M, int cap, int* cnt,
                                      float* os, int* oi, void* stream) {
-  if (nq <= 0 || nprobe <= 0 || cap <= 0) return (int)hipErrorInvalidValue;
-  dim3 grid((unsigned)nq * nprobe), block(256);
-  size_t lds = (size_t)M * 256 * sizeof(float);
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned char* c = (const unsigned char*)codes;
-#define GO(MM)                                                                                                      \
-  do {                                                                                                              \
-    (void)hipFuncSetAttribute((const void*)ivfpq_scan_thresh_kernel<MM>,                                            \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
-    hipLaunchKernelGGL((ivfpq_scan_thresh_kernel<MM>), grid, block, lds, st, c, list_off, probes, coarse, lut, thr, \
-                       nprobe, cap, cnt, os, oi);                                                                   \
-  } while (0)
-  switch (M) {
-    case 8: GO(8); break;
-    case 16: GO(16); break;
-    case 32: GO(32); break;
-    case 48: GO(48); break;
-    case 64: GO(64); break;
-    case 96: GO(96); break;
-    case 128: GO(128); break;
-    default: return (int)hipErrorInvalidValue;
-  }
-#undef GO
-  return (int)hipGetLastError();
+  return thresh_any<false>(codes, list_off, nullptr, probes, coarse, lut, thr, nq, nprobe, M, cap, cnt, os, oi,
+                           stream);
 }
 
 // partial lists: [nq, nprobe, kslot] (rows index the code array; -1 = empty)
 LZK_EXPORT int lzk_ivfpq_scan(const void* codes, const long* list_off, const int* probes, const float* coarse,
                               const float* lut, int nq, int nprobe, int M, int kslot, float* os, int* oi,
                               void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned char* c = (const unsigned char*)codes;
-  hipError_t e;
-  switch (kslot) {
-    case 1: e = launch_scan<1>(M, c, list_off, probes, coarse, lut, nq, nprobe, os, oi, st); break;
-    case 4: e = launch_scan<4>(M, c, list_off, probes, coarse, lut, nq, nprobe, os, oi, st); break;
-    case 10: e = launch_scan<10>(M, c, list_off, probes, coarse, lut, nq, nprobe, os, oi, st); break;
-    case 16: e = launch_scan<16>(M, c, list_off, probes, coarse, lut, nq, nprobe, os, oi, st); break;
-    default: return (int)hipErrorInvalidValue;
-  }
-  return (int)e;
+  return scan_any<false>(codes, list_off, nullptr, probes, coarse, lut, nq, nprobe, M, kslot, os, oi, stream);
+}
+
+// The filtered forms: foff [nlist + 1] offsets into frows, the passing code
+// rows in ascending order (lzk_ivfpq_filter_rows, ivfpq_filter.hip). Outputs
+// as above; the reported rows are code rows. Without both lists: refused.
+LZK_EXPORT int lzk_ivfpq_scan_f(const void* codes, const long* foff, const int* frows, const int* probes,
+                                const float* coarse, const float* lut, int nq, int nprobe, int M, int kslot,
+                                float* os, int* oi, void* stream) {
+  if (!foff || !frows) return (int)hipErrorInvalidValue;
+  return scan_any<true>(codes, foff, frows, probes, coarse, lut, nq, nprobe, M, kslot, os, oi, stream);
+}
+
+LZK_EXPORT int lzk_ivfpq_scan_deep_f(const void* codes, const long* foff, const int* frows, const int* probes,
+                                     const float* coarse, const float* lut, int nq, int nprobe, int M, float* os,
+                                     int* oi, void* stream) {
+  if (!foff || !frows) return (int)hipErrorInvalidValue;
+  return deep_any<true>(codes, foff, frows, probes, coarse, lut, nq, nprobe, M, os, oi, stream);
+}
+
+LZK_EXPORT int lzk_ivfpq_scan_thresh_f(const void* codes, const long* foff, const int* frows, const int* probes,
+                                       const float* coarse, const float* lut, const float* thr, int nq, int nprobe,
+                                       int M, int cap, int* cnt, float* os, int* oi, void* stream) {
+  if (!foff || !frows) return (int)hipErrorInvalidValue;
+  return thresh_any<true>(codes, foff, frows, probes, coarse, lut, thr, nq, nprobe, M, cap, cnt, os, oi, stream);
 }
 
 // Re-rank: V rows of ldv bytes (fmt 1 fp8 / 2 int8: D bytes + vscale[row];

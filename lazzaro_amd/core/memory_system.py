@@ -233,7 +233,7 @@ class MemorySystem(ConsolidationMixin):
             emb = OnDeviceEmbedder(cfg.embed_model, device=cfg.device, weights=cfg.embed_weights)
         kw.setdefault("index", cfg.index)
         kw.setdefault("index_params", {"nlist": cfg.nlist, "nprobe": cfg.nprobe, "pq_m": cfg.pq_m,
-                                       "ivf_min_rows": cfg.ivf_min_rows})
+                                       "ivf_min_rows": cfg.ivf_min_rows, "ivf_filtered": cfg.ivf_filtered})
         kw.setdefault("hierarchy_mode", cfg.hierarchy_mode)
         kw.setdefault("hierarchy_params", {"fine": cfg.hierarchy_fine, "top": cfg.hierarchy_top,
                                            "every": cfg.hierarchy_every})
@@ -787,7 +787,7 @@ class MemorySystem(ConsolidationMixin):
                 "rows_reclaimed_total": g.rows_reclaimed_total, "ann_removed": g.ann_removed,
                 "ann_upserts": g.ann_upserts, "ann_rebuilds": g.ann_rebuilds,
                 "filtered_searches": g.filtered_searches, "filter_plans_built": g.filter_plans_built,
-                "filtered_sparse": g.filtered_sparse, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
+                "filtered_sparse": g.filtered_sparse, "filtered_ann": g.filtered_ann, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
                 "avg_search_batch_ms": round(sms / m["search_batches"], 3) if m.get("search_batches") else 0.0}
 
     def _graph_bytes(self) -> int:

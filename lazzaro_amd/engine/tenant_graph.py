@@ -176,6 +176,14 @@ COMPACT_KERNEL = True
 # each width. The dense time grows with the tenant, so on tenants well below
 # 2M rows this limit is generous and well above it conservative (not measured).
 FILTER_SPARSE_MAX_ROWS = 1 << 19
+# the filtered IVF-PQ route (ann_cfg["filtered"]) serves a filter that passes at
+# least 1 / FILTER_ANN_MAX_SCALE of the tenant's rows: it probes n / count times
+# the lists. A cap on that cost, not a speed crossover: measured
+# (profiles/r11/filtered_ivfpq/), whether the route beats the dense masked scan
+# depends on the batch and the tenant's size -- never at 2M x 768 rows, 2.2x
+# faster at 8M rows for one query at every fraction, slower for 1,024 queries --
+# while its time grows with the scale and recall@10 slipped below 0.998 at scale 32
+FILTER_ANN_MAX_SCALE = 8
 FILTER_PLAN_CACHE = 8  # plans kept per graph (LRU); a plan holds 4 n bytes of bias + 4 bytes per listed row
 
 
@@ -329,10 +337,11 @@ class FilterPlan:
     """A filter evaluated over one tenant state: the per-row score bias
     (store bias where the row passes, -inf elsewhere), the passing rows in
     ascending order (int32, device) and their number."""
-    __slots__ = ("bias", "rows", "count")
+    __slots__ = ("bias", "rows", "count", "ann_lists")
 
     def __init__(self, bias: torch.Tensor, rows: torch.Tensor, count: int):
         self.bias, self.rows, self.count = bias, rows, count
+        self.ann_lists = None  # the IVF-PQ index's FilteredLists of this plan (the filtered index route)
 
 
 class TenantGraph:
@@ -2477,7 +2486,7 @@ class TenantGraph:
     _tcode_dirty = None  # rows whose type was rewritten since the column was synced
     type_code = None  # type name -> code, in order of first appearance
     _filter_plans = None  # OrderedDict: plan key -> FilterPlan (LRU, FILTER_PLAN_CACHE entries)
-    filtered_searches = filter_plans_built = filtered_sparse = 0
+    filtered_searches = filter_plans_built = filtered_sparse = filtered_ann = 0
 
     def _type_rewritten(self, r: int) -> None:
         """The type of row ``r`` changed: its code is re-written, and cached
@@ -2592,10 +2601,18 @@ class TenantGraph:
         FILTER_SPARSE_MAX_ROWS -> the indexed fp32 scan of the listed rows +
         the exact re-rank (its result never consults ``_nodes_marked``: every
         listed row is a node); otherwise the dense flow of
-        :meth:`_store_search` with the plan's bias as its row mask. A tenant
-        with an IVF-PQ index takes these flat routes too when filtered: the
-        index's candidate lists know nothing of the predicate, and masking
-        them afterwards would lose recall."""
+        :meth:`_store_search` with the plan's bias as its row mask. Masking
+        an IVF-PQ index's candidates afterwards would lose recall in
+        proportion to the selectivity, so a tenant with an index takes these
+        flat routes too -- unless ``ann_cfg["filtered"]`` is set: then a plan
+        too long for the indexed scan that passes at least 1 /
+        FILTER_ANN_MAX_SCALE of a large unit-row tenant goes to the index
+        with the predicate pushed into the list scan: the passing code rows
+        of each list (IVFPQIndex.filter_rows over the plan's bias, cached on
+        the plan until the index's ``order_gen`` moves), ``filtered_nprobe``
+        lists probed, the exact PQ top-R among passing rows re-ranked in fp32
+        with the plan's bias as row mask (every returned row passes whatever
+        the lists held)."""
         from ..core.filters import MemoryFilter
         flt = MemoryFilter.coerce(where)
         n = self.n
@@ -2620,6 +2637,15 @@ class TenantGraph:
                 Qf = Qf / torch.where(qn > 0, qn, torch.ones_like(qn))
             _, cand = gather_topk(self.emb32, plan.rows, plan.count, Qf, CAND_SLOTS, plan.bias,
                                   2.0 if metric == "l2" else 1.0)
+            return self._rerank_store(Qf, cand, k, metric, plan.bias)
+        cfg = self.ann_cfg
+        if cfg is not None and cfg.get("filtered") and n >= cfg["min_rows"] and self.unit_rows() \
+                and n <= FILTER_ANN_MAX_SCALE * plan.count:
+            self.filtered_ann += 1
+            if metric == "cosine":
+                qn = Qf.norm(dim=1, keepdim=True)
+                Qf = Qf / torch.where(qn > 0, qn, torch.ones_like(qn))
+            cand = self._ann_candidates(Qf, max(cfg.get("rerank", 1024), k), cfg, plan)
             return self._rerank_store(Qf, cand, k, metric, plan.bias)
         return self._store_search(Qf, k, metric, False, plan)
 
@@ -2662,7 +2688,7 @@ class TenantGraph:
             return self._rerank_store(Qf, cand, k, metric, bias, node_rows)
         return self._exact_store(Qf, k, metric, bias)
 
-    def _ann_candidates(self, Qf: torch.Tensor, R: int, cfg: Dict) -> torch.Tensor:
+    def _ann_candidates(self, Qf: torch.Tensor, R: int, cfg: Dict, plan=None) -> torch.Tensor:
         """Graph rows [M, R] from the tenant's IVF-PQ index, built on first
         use over the unit rows (ids = rows) and extended with the rows
         appended since, and maintained in place from then on (no re-train,
@@ -2677,7 +2703,12 @@ class TenantGraph:
         * :meth:`compact` renumbers the index's ids through its row remap.
 
         Rebuilt only for what that cannot express: a reload, or rows that
-        vanished without a compaction (``_ann_covered > n``)."""
+        vanished without a compaction (``_ann_covered > n``).
+
+        ``plan`` (a FilterPlan of this tenant state): the candidates are the
+        exact PQ top-R among the passing rows of ``filtered_nprobe`` probed
+        lists. The plan's bias column is the id mask as it is (ids = rows);
+        ids are unique among live vectors, so ``plan.count`` bounds the list."""
         from ..index.ivfpq import IVFPQIndex
         n = self.n
         idx = self._ann
@@ -2722,6 +2753,13 @@ class TenantGraph:
                 self.ann_removed += idx.remove(rows)
                 dead[rows] = 1
             self._ann_synced = self._store_version
+        if plan is not None:
+            from ..index.ivfpq import filtered_nprobe
+            idx._finalize()
+            fl = plan.ann_lists
+            if fl is None or fl.gen != idx.order_gen:
+                fl = plan.ann_lists = idx.filter_rows(plan.bias, max_rows=plan.count, keep_mask=False)
+            return idx.candidate_ids(Qf, R, filtered_nprobe(cfg["nprobe"], idx.nlist, n, plan.count), allow=fl)
         return idx.candidate_ids(Qf, R, cfg["nprobe"])
 
     def _ann_dead_flags(self, c: int) -> torch.Tensor:

@@ -15,6 +15,11 @@ storage. Inner-product metric on unit vectors (cosine).
           ``topk_merge`` kernel; deep lists (re-rank depth > 16) from
           ``ivfpq_scan_deep`` (each wave's best rows per list); optional exact
           re-rank of the candidates against kept bf16/fp8 rows.
+* filter: ``filter_rows(allow)`` compacts the code rows whose id passes a mask
+          into per-list row lists (ivfpq_filter.hip); ``search`` /
+          ``candidate_ids`` with ``allow=`` then scan the passing rows of the
+          probed lists only (the ``_f`` scans of ivfpq.hip, one indirection
+          per scored row) -- the exact PQ top-k / top-R among passing rows.
 * maintain: ``remove(ids)``, ``upsert(ids, x)`` and ``translate_ids(table)``
           delete, rewrite and renumber vectors without a re-train or a
           re-encode of the rest. They only flag rows and append code rows; the
@@ -28,6 +33,7 @@ CPU tensors run a torch reference of the same pipeline (tests).
 """
 from __future__ import annotations
 
+import itertools
 from typing import Optional, Tuple
 
 import numpy as np
@@ -50,7 +56,21 @@ _lib.register("lzk_ivfpq_scan_thresh", _lib.I, [_lib.P, _lib.P, _lib.P, _lib.P, 
 _lib.register("lzk_rerank", _lib.I, [_lib.P, _lib.L, _lib.I, _lib.P, _lib.P, _lib.I, _lib.I, _lib.P, _lib.I,
                                       _lib.I, _lib.I, _lib.P, _lib.P, _lib.P])
 
+_lib.register("lzk_ivfpq_scan_f", _lib.I, [_lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.I, _lib.I, _lib.I,
+                                            _lib.I, _lib.P, _lib.P, _lib.P])
+_lib.register("lzk_ivfpq_scan_deep_f", _lib.I, [_lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.I, _lib.I,
+                                                 _lib.I, _lib.P, _lib.P, _lib.P])
+_lib.register("lzk_ivfpq_scan_thresh_f", _lib.I, [_lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.P, _lib.I,
+                                                   _lib.I, _lib.I, _lib.I, _lib.P, _lib.P, _lib.P, _lib.P])
+_lib.register("lzk_ivfpq_filter_rows_ws", _lib.L, [_lib.L])
+_lib.register("lzk_ivfpq_filter_rows", _lib.I, [_lib.P, _lib.P, _lib.L, _lib.P, _lib.I, _lib.L, _lib.P, _lib.I,
+                                                 _lib.L, _lib.P, _lib.P, _lib.P, _lib.P])
+
 KSLOTS = (1, 4, 10, 16)
+
+# order_gen values: unique over every index of the process, so lists built for
+# one index never look current to another (a tenant's rebuilt index)
+_GEN = itertools.count(1)
 
 # _finalize on the GPU: flagged rows leave and the appended tail is merged in
 # place by the HIP kernels (compact.hip, ivfmaint.hip); MAINT_KERNEL = False:
@@ -67,6 +87,25 @@ def _kslot(k: int) -> int:
 
 def _unit(x):
     return x / x.norm(dim=1, keepdim=True).clamp_min(1e-30)
+
+
+def filtered_nprobe(nprobe: int, nlist: int, n: int, count: int) -> int:
+    """Lists to probe when ``count`` of ``n`` rows pass a filter: a filter
+    passing 1/s of the rows leaves 1/s of each list, so s times the lists
+    keep the number of scanned passing rows level -- capped at ``nlist``."""
+    return min(nlist, -(-nprobe * n // max(count, 1)))
+
+
+class FilteredLists:
+    """The code rows of an index that pass a filter, per list: ``rows``
+    (int32, ascending code rows, CSR order) and ``off`` (int64 [nlist + 1]
+    offsets into ``rows``; ``off[nlist]`` = the number of listed rows). Valid
+    while the index's ``order_gen`` equals ``gen``; ``allow`` is the mask they
+    were built from (None: not kept, a stale object cannot be rebuilt)."""
+    __slots__ = ("rows", "off", "gen", "allow", "max_rows")
+
+    def __init__(self, rows, off, gen, allow=None, max_rows=None):
+        self.rows, self.off, self.gen, self.allow, self.max_rows = rows, off, gen, allow, max_rows
 
 
 class IVFPQIndex:
@@ -110,6 +149,8 @@ class IVFPQIndex:
         self._vscale = None
         self.list_off = z(nlist + 1, dt=torch.int64)
         self._dirty = False
+        # bumps whenever the code rows, their order or their ids may have changed (what FilteredLists depend on)
+        self.order_gen = next(_GEN)
 
     # ------------------------------------------------------------------ storage
     def reserve(self, n: int) -> None:
@@ -153,6 +194,7 @@ class IVFPQIndex:
         # a hand-built index is in CSR order already (list_off is set beside it)
         self.nv = self._sorted_n = self._nlive = self.n
         self._cdead = self._vdead = None
+        self.order_gen = next(_GEN)
 
     @property
     def list_of(self) -> torch.Tensor:
@@ -171,6 +213,7 @@ class IVFPQIndex:
     def ids(self, v: torch.Tensor) -> None:
         self._vids = v.to(self.device, torch.int64)
         self._pos = torch.arange(v.shape[0], device=self.device)
+        self.order_gen = next(_GEN)
 
     @property
     def vectors(self):
@@ -279,6 +322,7 @@ class IVFPQIndex:
             self.nv = v0 + n
             self._nlive += n
         self._dirty = True
+        self.order_gen = next(_GEN)
 
     # ------------------------------------------------------------------ maintain
     def _flags(self, which: str) -> torch.Tensor:
@@ -316,6 +360,7 @@ class IVFPQIndex:
         ids = torch.unique(torch.as_tensor(ids, dtype=torch.int64).to(self.device).flatten())
         rows, _ = self._lookup(ids)
         k = int(rows.numel())
+        self.order_gen = next(_GEN)
         if k:
             self._flags("_vdead")[rows] = 1
             self._nlive -= k
@@ -330,6 +375,7 @@ class IVFPQIndex:
         ids that were already held."""
         ids = torch.as_tensor(ids, dtype=torch.int64).to(self.device).flatten()
         assert ids.numel() == x.shape[0]
+        self.order_gen = next(_GEN)
         if ids.numel() == 0:
             return 0
         uid, inv = torch.unique(ids, return_inverse=True)
@@ -357,6 +403,7 @@ class IVFPQIndex:
         the vector (a compaction of the caller's id space). ``table``: an
         integer tensor on any device, indexed by the current ids."""
         nv = self.nv
+        self.order_gen = next(_GEN)
         if nv == 0:
             return
         t = torch.as_tensor(table).to(self.device, torch.int64).flatten()
@@ -380,6 +427,7 @@ class IVFPQIndex:
         sort and permuted in chunks into one new buffer. The vector rows keep
         their order (``pos`` follows the codes)."""
         n, nv = self.n, self.nv
+        self.order_gen = next(_GEN)
         if self._cdead is not None or self._vdead is not None:
             keep = torch.ones(n, dtype=torch.bool, device=self.device)
             if self._cdead is not None:
@@ -435,6 +483,7 @@ class IVFPQIndex:
         ops.tenant_ops.rc_chunk_rows)."""
         if not self._dirty:
             return
+        self.order_gen = next(_GEN)  # rows are about to move
         if not (self.device.type == "cuda" and MAINT_KERNEL and self._sorted_n > 0):
             return self._finalize_ref()
         from ..ops import ivf_ops as V
@@ -520,12 +569,74 @@ class IVFPQIndex:
             b += n * self._vec.shape[1] * self._vec.element_size()
         return b + (n * 4 if self._vscale is not None else 0)
 
+    # ------------------------------------------------------------------ filter
+    def filter_rows(self, allow: torch.Tensor, max_rows: Optional[int] = None, keep_mask: bool = True) -> FilteredLists:
+        """The passing code rows of every list (:class:`FilteredLists`).
+        ``allow`` is indexed by id: a bool / uint8 tensor (non-zero passes) or
+        an fp32 score bias (above -inf passes; a filter plan's bias column as
+        it is). An id outside it does not pass -- so ids must be small and
+        non-negative, as a TenantGraph's are (ids = rows). ``max_rows``: the
+        capacity of the row list (default ``n``, which cannot overflow; a
+        caller that knows the passing count may pass it -- were more rows to
+        pass, the lists stop at ``max_rows``, nothing is written past it). On
+        the GPU three launches and a lower bound per list (ivfpq_filter.hip),
+        no host synchronisation; CPU tensors take the torch formulation."""
+        self._finalize()
+        n = self.n
+        a = allow.to(self.device)
+        if a.dtype == torch.bool:
+            a = a.view(torch.uint8)
+        if a.dtype not in (torch.uint8, torch.float32):
+            raise TypeError("allow: a bool / uint8 mask or an fp32 bias")
+        a = a.flatten().contiguous()
+        kind = 1 if a.dtype == torch.float32 else 0
+        n_ids = int(a.numel())
+        cap = n if max_rows is None else int(max_rows)
+        if self.device.type != "cuda":
+            if n and n_ids:
+                ids = self._vids[self._pos[:n]]
+                v = a[ids.clamp(0, n_ids - 1)]
+                ok = (ids >= 0) & (ids < n_ids) & ((v > float("-inf")) if kind else (v != 0))
+                rows = torch.nonzero(ok).flatten()[:cap]
+            else:
+                rows = torch.zeros(0, dtype=torch.int64, device=self.device)
+            off = torch.searchsorted(rows, self.list_off.contiguous())
+            return FilteredLists(rows.to(torch.int32), off.to(torch.int64), self.order_gen,
+                                 allow if keep_mask else None, max_rows)
+        L = _lib.lib()
+        frows = torch.empty(max(cap, 1), dtype=torch.int32, device=self.device)
+        foff = torch.empty(self.nlist + 1, dtype=torch.int64, device=self.device)
+        ws = torch.empty(max(int(L.lzk_ivfpq_filter_rows_ws(n)), 1), dtype=torch.int32, device=self.device)
+        _lib.check(L.lzk_ivfpq_filter_rows(self._pos.data_ptr(), self._vids.data_ptr(), n, a.data_ptr(), kind, n_ids,
+                                           self.list_off.data_ptr(), self.nlist, cap, frows.data_ptr(),
+                                           foff.data_ptr(), ws.data_ptr(), _lib.stream_ptr(self.device)),
+                   "lzk_ivfpq_filter_rows")
+        return FilteredLists(frows, foff, self.order_gen, allow if keep_mask else None, max_rows)
+
+    def _lists(self, allow) -> Optional[FilteredLists]:
+        """``allow`` of a search as current lists (after ``_finalize``): a
+        mask is compacted now; stale lists are rebuilt in place from the mask
+        they carry, or refused."""
+        if allow is None:
+            return None
+        if not isinstance(allow, FilteredLists):
+            return self.filter_rows(allow)
+        if allow.gen != self.order_gen:
+            if allow.allow is None:
+                raise ValueError("FilteredLists are stale (the index changed since filter_rows) and carry no mask")
+            fresh = self.filter_rows(allow.allow, allow.max_rows)
+            allow.rows, allow.off, allow.gen = fresh.rows, fresh.off, fresh.gen
+        return allow
+
     # ------------------------------------------------------------------ search
-    def search(self, q: torch.Tensor, k: int = 10, nprobe: int = 16, rerank: int = 0):
+    def search(self, q: torch.Tensor, k: int = 10, nprobe: int = 16, rerank: int = 0, allow=None):
         """Returns (scores fp32 [nq, k], ids int64 [nq, k]). ``rerank`` > 0:
         the best ``rerank`` PQ candidates are re-scored exactly against the
-        kept copy (scores then are exact inner products)."""
+        kept copy (scores then are exact inner products). ``allow`` (a mask
+        as :meth:`filter_rows` takes it, or its :class:`FilteredLists`): only
+        vectors whose id passes are scanned, ranked and returned."""
         self._finalize()
+        fl = self._lists(allow)
         qf = _unit(q.to(self.device).float())
         nq = qf.shape[0]
         nprobe = min(nprobe, self.nlist)
@@ -534,13 +645,13 @@ class IVFPQIndex:
         lut = torch.einsum("qmd,mcd->qmc", qf.view(nq, self.m, self.dsub), self.codebooks).contiguous()
         kk = max(k, rerank) if rerank else k
         if self.device.type != "cuda":
-            s, rows = self._scan_ref(probes, coarse, lut, kk)
+            s, rows = self._scan_ref(probes, coarse, lut, kk, fl)
         elif rerank and self._vec is not None and kk > KSLOTS[-1]:
-            s, rows = self._scan_candidates(probes.to(torch.int32).contiguous(), coarse.contiguous(), lut, kk)
+            s, rows = self._scan_candidates(probes.to(torch.int32).contiguous(), coarse.contiguous(), lut, kk, fl)
         elif kk <= KSLOTS[-1]:
-            s, rows = self._scan_gpu(probes.to(torch.int32).contiguous(), coarse.contiguous(), lut, kk)
+            s, rows = self._scan_gpu(probes.to(torch.int32).contiguous(), coarse.contiguous(), lut, kk, fl)
         else:
-            s, rows = self._scan_deep(probes.to(torch.int32).contiguous(), coarse.contiguous(), lut, kk)
+            s, rows = self._scan_deep(probes.to(torch.int32).contiguous(), coarse.contiguous(), lut, kk, fl)
         if rerank and self._vec is not None:
             vrows = torch.where(rows >= 0, self._pos[rows.clamp_min(0)], torch.full_like(rows, -1))
             if self._rerank_gpu_ok(k) and self._rerank_fits(vrows.shape[1]):
@@ -563,22 +674,24 @@ class IVFPQIndex:
         ids = torch.where(rows >= 0, self._vids[self._pos[rows.clamp_min(0)]], torch.full_like(rows, -1))
         return s, ids
 
-    def candidate_ids(self, q: torch.Tensor, R: int, nprobe: int = 16) -> torch.Tensor:
+    def candidate_ids(self, q: torch.Tensor, R: int, nprobe: int = 16, allow=None) -> torch.Tensor:
         """The ids of the exact PQ top-``R`` rows over the ``nprobe`` probed
         lists per query ([nq, R] int64, -1 padded) -- for a caller that
-        re-ranks with its own exact vectors (TenantGraph's fp32 rows)."""
+        re-ranks with its own exact vectors (TenantGraph's fp32 rows).
+        ``allow`` as in :meth:`search`: the top-``R`` among passing rows."""
         self._finalize()
+        fl = self._lists(allow)
         qf = _unit(q.to(self.device).float())
         nq = qf.shape[0]
         nprobe = min(nprobe, self.nlist)
         coarse, probes = torch.topk(qf @ self.centroids.T, nprobe, dim=1)
         lut = torch.einsum("qmd,mcd->qmc", qf.view(nq, self.m, self.dsub), self.codebooks).contiguous()
         if self.device.type != "cuda":
-            _, rows = self._scan_ref(probes, coarse, lut, R)
+            _, rows = self._scan_ref(probes, coarse, lut, R, fl)
         elif R <= KSLOTS[-1]:
-            _, rows = self._scan_gpu(probes.to(torch.int32).contiguous(), coarse.contiguous(), lut, R)
+            _, rows = self._scan_gpu(probes.to(torch.int32).contiguous(), coarse.contiguous(), lut, R, fl)
         else:
-            _, rows = self._scan_candidates(probes.to(torch.int32).contiguous(), coarse.contiguous(), lut, R)
+            _, rows = self._scan_candidates(probes.to(torch.int32).contiguous(), coarse.contiguous(), lut, R, fl)
         rows = rows.long()
         return torch.where(rows >= 0, self._vids[self._pos[rows.clamp_min(0)]], torch.full_like(rows, -1))
 
@@ -616,7 +729,9 @@ class IVFPQIndex:
                                          oi.data_ptr(), _lib.stream_ptr(self.device)), "lzk_rerank")
         return os_, oi
 
-    def _scan_ref(self, probes, coarse, lut, k):
+    def _scan_ref(self, probes, coarse, lut, k, fl: Optional[FilteredLists] = None):
+        """``fl``: the lists are ``fl.rows[fl.off[l]:fl.off[l + 1]]`` -- here
+        and in the three GPU scans below, which then call the ``_f`` kernels."""
         nq = probes.shape[0]
         out_s = torch.full((nq, k), float("-inf"), device=self.device)
         out_r = torch.full((nq, k), -1, dtype=torch.long, device=self.device)
@@ -626,12 +741,14 @@ class IVFPQIndex:
             cand_s, cand_r = [], []
             for p in range(probes.shape[1]):
                 l = int(probes[qi, p])
-                r0, r1 = int(self.list_off[l]), int(self.list_off[l + 1])
+                off = self.list_off if fl is None else fl.off
+                r0, r1 = int(off[l]), int(off[l + 1])
                 if r1 == r0:
                     continue
-                c = codes[r0:r1].long()
+                rr = torch.arange(r0, r1, device=self.device) if fl is None else fl.rows[r0:r1].long()
+                c = codes[rr].long()
                 cand_s.append(coarse[qi, p] + lut[qi][ar[None, :], c].sum(1))
-                cand_r.append(torch.arange(r0, r1, device=self.device))
+                cand_r.append(rr)
             if not cand_s:
                 continue
             cs_, cr_ = torch.cat(cand_s), torch.cat(cand_r)
@@ -640,7 +757,7 @@ class IVFPQIndex:
             out_r[qi, : o.numel()] = cr_[o]
         return out_s, out_r
 
-    def _scan_deep(self, probes, coarse, lut, k):
+    def _scan_deep(self, probes, coarse, lut, k, fl: Optional[FilteredLists] = None):
         """Deep candidate lists (re-rank depth >> 16): each (query, probed
         list) block emits its waves' best rows (``ivfpq_scan_deep_kernel``,
         4 x 128 per list), then a top-k over the query's nprobe x 512 PQ scores."""
@@ -649,9 +766,15 @@ class IVFPQIndex:
         W = L.lzk_ivfpq_deep_width()
         os_ = torch.empty((nq, nprobe * W), dtype=torch.float32, device=self.device)
         oi = torch.empty((nq, nprobe * W), dtype=torch.int32, device=self.device)
-        _lib.check(L.lzk_ivfpq_scan_deep(self._codes.data_ptr(), self.list_off.data_ptr(), probes.data_ptr(),
-                                         coarse.data_ptr(), lut.data_ptr(), nq, nprobe, self.m, os_.data_ptr(),
-                                         oi.data_ptr(), _lib.stream_ptr(self.device)), "lzk_ivfpq_scan_deep")
+        if fl is None:
+            _lib.check(L.lzk_ivfpq_scan_deep(self._codes.data_ptr(), self.list_off.data_ptr(), probes.data_ptr(),
+                                             coarse.data_ptr(), lut.data_ptr(), nq, nprobe, self.m, os_.data_ptr(),
+                                             oi.data_ptr(), _lib.stream_ptr(self.device)), "lzk_ivfpq_scan_deep")
+        else:
+            _lib.check(L.lzk_ivfpq_scan_deep_f(self._codes.data_ptr(), fl.off.data_ptr(), fl.rows.data_ptr(),
+                                               probes.data_ptr(), coarse.data_ptr(), lut.data_ptr(), nq, nprobe,
+                                               self.m, os_.data_ptr(), oi.data_ptr(), _lib.stream_ptr(self.device)),
+                       "lzk_ivfpq_scan_deep_f")
         kk = min(k, os_.shape[1])
         s, j = torch.topk(os_, kk, dim=1)
         rows = torch.gather(oi, 1, j).long()
@@ -667,26 +790,35 @@ class IVFPQIndex:
     CAND_CAP = 16
     CAND_MIN = 32768
 
-    def _scan_candidates(self, probes, coarse, lut, R):
+    def _scan_candidates(self, probes, coarse, lut, R, fl: Optional[FilteredLists] = None):
         """Re-rank candidates: the exact PQ top-R over the probed lists (plus
         ties). Pass 1 (``ivfpq_scan_deep``) pools each list's best rows; the
         R-th best pooled score is a lower bound of the true R-th best; pass 2
         (``ivfpq_scan_thresh``) appends EVERY probed row at or above it, so a
         query whose neighbours crowd into one list still gets all of them.
         Returns (PQ scores, code rows) [nq, R] of the collected rows' PQ
-        top-R, -1 padded."""
+        top-R, -1 padded. With ``fl`` both passes see passing rows only: the
+        pooled R-th best passing score bounds the true one from below, and
+        the result is the exact PQ top-R among the passing rows."""
         nq, nprobe = probes.shape
-        ps, _ = self._scan_deep(probes, coarse, lut, R)
+        ps, _ = self._scan_deep(probes, coarse, lut, R, fl)
         thr = ps[:, R - 1].contiguous()  # -inf when the pools hold fewer than R rows: take everything
         cap = max(self.CAND_CAP * R, self.CAND_MIN)
         L = _lib.lib()
         cnt = torch.zeros(nq, dtype=torch.int32, device=self.device)
         os_ = torch.empty((nq, cap), dtype=torch.float32, device=self.device)
         oi = torch.empty((nq, cap), dtype=torch.int32, device=self.device)
-        _lib.check(L.lzk_ivfpq_scan_thresh(self._codes.data_ptr(), self.list_off.data_ptr(), probes.data_ptr(),
-                                           coarse.data_ptr(), lut.data_ptr(), thr.data_ptr(), nq, nprobe, self.m,
-                                           cap, cnt.data_ptr(), os_.data_ptr(), oi.data_ptr(),
-                                           _lib.stream_ptr(self.device)), "lzk_ivfpq_scan_thresh")
+        if fl is None:
+            _lib.check(L.lzk_ivfpq_scan_thresh(self._codes.data_ptr(), self.list_off.data_ptr(), probes.data_ptr(),
+                                               coarse.data_ptr(), lut.data_ptr(), thr.data_ptr(), nq, nprobe, self.m,
+                                               cap, cnt.data_ptr(), os_.data_ptr(), oi.data_ptr(),
+                                               _lib.stream_ptr(self.device)), "lzk_ivfpq_scan_thresh")
+        else:
+            _lib.check(L.lzk_ivfpq_scan_thresh_f(self._codes.data_ptr(), fl.off.data_ptr(), fl.rows.data_ptr(),
+                                                 probes.data_ptr(), coarse.data_ptr(), lut.data_ptr(),
+                                                 thr.data_ptr(), nq, nprobe, self.m, cap, cnt.data_ptr(),
+                                                 os_.data_ptr(), oi.data_ptr(), _lib.stream_ptr(self.device)),
+                       "lzk_ivfpq_scan_thresh_f")
         self.last_candidates = cnt  # per-query count (> cap: overflowed, kept the first cap)
         valid = torch.arange(cap, device=self.device)[None, :] < cnt.clamp(max=cap)[:, None]
         sc = torch.where(valid, os_, torch.full_like(os_, float("-inf")))
@@ -694,7 +826,7 @@ class IVFPQIndex:
         rows = torch.gather(oi, 1, j).long()
         return ts, torch.where(torch.isneginf(ts), torch.full_like(rows, -1), rows)
 
-    def _scan_gpu(self, probes, coarse, lut, k):
+    def _scan_gpu(self, probes, coarse, lut, k, fl: Optional[FilteredLists] = None):
         nq, nprobe = probes.shape
         ks = _kslot(k)
         part = nq * nprobe * ks
@@ -703,9 +835,14 @@ class IVFPQIndex:
         pi = ws[part * 4: part * 8].view(torch.int32)
         st = _lib.stream_ptr(self.device)
         L = _lib.lib()
-        _lib.check(L.lzk_ivfpq_scan(self._codes.data_ptr(), self.list_off.data_ptr(), probes.data_ptr(),
-                                    coarse.data_ptr(), lut.data_ptr(), nq, nprobe, self.m, ks, ps.data_ptr(),
-                                    pi.data_ptr(), st), "lzk_ivfpq_scan")
+        if fl is None:
+            _lib.check(L.lzk_ivfpq_scan(self._codes.data_ptr(), self.list_off.data_ptr(), probes.data_ptr(),
+                                        coarse.data_ptr(), lut.data_ptr(), nq, nprobe, self.m, ks, ps.data_ptr(),
+                                        pi.data_ptr(), st), "lzk_ivfpq_scan")
+        else:
+            _lib.check(L.lzk_ivfpq_scan_f(self._codes.data_ptr(), fl.off.data_ptr(), fl.rows.data_ptr(),
+                                          probes.data_ptr(), coarse.data_ptr(), lut.data_ptr(), nq, nprobe, self.m,
+                                          ks, ps.data_ptr(), pi.data_ptr(), st), "lzk_ivfpq_scan_f")
         os_ = torch.empty((nq, k), dtype=torch.float32, device=self.device)
         oi = torch.empty((nq, k), dtype=torch.long, device=self.device)
         _lib.check(L.lzk_topk_merge(ps.data_ptr(), pi.data_ptr(), nprobe * ks, nq, ks, k, 0, os_.data_ptr(),
