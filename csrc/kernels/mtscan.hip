@@ -107,14 +107,19 @@ __global__ __launch_bounds__(128) void mt_sample_kernel(const long* __restrict__
 // tile, -1 = none): score = 2<q,x> + bias[row] - |q|^2 (L2, metric 0) or
 // <q,x> + bias[row] (ip, metric 1) from the tenant's fp32 rows; top-k by
 // (score desc, key asc), key = slot << 32 | row; then rows that are not live
-// nodes become (-inf, -1), as the per-tenant path filters its results. One
-// wave per query, 4 lanes per candidate (store_rerank_kernel's layout).
+// nodes become (-inf, -1), as the per-tenant path filters its results; redo[q]
+// (optional) is set to 1 when that happened to one of the k ranks -- the query
+// lost a result slot to a row the per-tenant path would have replaced from
+// another tenant, so the caller has to recompute it -- and is left alone
+// otherwise. One wave per query, 4 lanes per candidate (store_rerank_kernel's
+// layout).
 __global__ __launch_bounds__(256) void mt_rerank_kernel(const float* __restrict__ Q, long ldq, int D,
                                                         const long* __restrict__ cand, int C, int M, int k,
                                                         const int* __restrict__ t_slot, const int* __restrict__ t_row0,
                                                         const long* __restrict__ p_e32, const long* __restrict__ p_bias,
                                                         const long* __restrict__ p_kind, int metric,
-                                                        float* __restrict__ os, long* __restrict__ okey) {
+                                                        float* __restrict__ os, long* __restrict__ okey,
+                                                        int* __restrict__ redo) {
   const int lane = threadIdx.x & 63;
   const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (q >= M) return;
@@ -172,12 +177,15 @@ __global__ __launch_bounds__(256) void mt_rerank_kernel(const float* __restrict_
     if (l2 && o != lane && (s2 > my_s || (s2 == my_s && k2 < my_k))) ++rank;
   }
   const int nlive = __popcll(__ballot(live));
+  bool ghost = false;
   if (live && rank < k) {
     const int slot = (int)(my_k >> 32), row = (int)(my_k & 0xFFFFFFFF);
     const bool node = reinterpret_cast<const unsigned char*>(p_kind[slot])[row] == MT_NODE;
     os[(long)q * k + rank] = node ? my_s : LZK_NEG_INF;
     okey[(long)q * k + rank] = node ? my_k : -1;
+    ghost = !node;
   }
+  if (redo != nullptr && __ballot(ghost) != 0 && lane == 0) redo[q] = 1;
   for (int j = nlive + lane; j < k; j += 64) {
     os[(long)q * k + j] = LZK_NEG_INF;
     okey[(long)q * k + j] = -1;
@@ -214,9 +222,9 @@ LZK_EXPORT int lzk_mt_sample(const long* t_x, const long* t_b, const int* s_tile
 
 LZK_EXPORT int lzk_mt_rerank(const float* Q, long ldq, int D, const long* cand, int C, int M, int k, const int* t_slot,
                              const int* t_row0, const long* p_e32, const long* p_bias, const long* p_kind, int metric,
-                             float* os, long* okey, void* stream) {
+                             float* os, long* okey, int* redo, void* stream) {
   if (C <= 0 || C > 64 || k <= 0 || k > C || M <= 0 || ldq < D) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(mt_rerank_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, Q, ldq, D,
-                     cand, C, M, k, t_slot, t_row0, p_e32, p_bias, p_kind, metric, os, okey);
+                     cand, C, M, k, t_slot, t_row0, p_e32, p_bias, p_kind, metric, os, okey, redo);
   return (int)hipGetLastError();
 }

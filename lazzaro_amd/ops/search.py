@@ -1035,7 +1035,7 @@ _lib.register("lzk_mt_cand", _lib.I, [_lib.P, _lib.P, _lib.P, _lib.I, _lib.L, _l
 _lib.register("lzk_mt_sample", _lib.I, [_lib.P, _lib.P, _lib.P, _lib.P, _lib.I, _lib.L, _lib.I, _lib.P, _lib.P,
                                         _lib.P])
 _lib.register("lzk_mt_rerank", _lib.I, [_lib.P, _lib.L, _lib.I, _lib.P, _lib.I, _lib.I, _lib.I, _lib.P, _lib.P,
-                                        _lib.P, _lib.P, _lib.P, _lib.I, _lib.P, _lib.P, _lib.P])
+                                        _lib.P, _lib.P, _lib.P, _lib.I, _lib.P, _lib.P, _lib.P, _lib.P])
 MT_TILE = 256
 MT_STRIDE = 64  # the threshold sample: rows 0, 64, 128, 192 of every tile
 
@@ -1044,12 +1044,18 @@ class MtTiles:
     """Tile table of a set of tenants (host-built, uploaded once per change):
     tile t = rows [row0[t], row0[t] + n[t]) (n <= 256) of tenant slot
     ``slot[t]``; ``x`` / ``b`` the addresses of its first bf16 row / store
-    bias entry. ``s_tile`` / ``s_row``: the strided threshold sample."""
+    bias entry. ``s_tile`` / ``s_row``: the strided threshold sample. Tiles
+    are laid out in ascending slot order whatever order the tenants come in,
+    so candidate-id order (tile * 256 + row) is result-key order (slot << 32 |
+    row): the candidate select's tie-break keeps the rows the result order
+    ranks first."""
 
     def __init__(self, slots: np.ndarray, nrows: np.ndarray, e16: np.ndarray, bias: np.ndarray, ld16: int,
                  device):
-        nrows = np.asarray(nrows, np.int64)
-        keep = nrows > 0
+        slots, nrows = np.asarray(slots, np.int64), np.asarray(nrows, np.int64)
+        e16, bias = np.asarray(e16, np.int64), np.asarray(bias, np.int64)
+        keep = np.nonzero(nrows > 0)[0]
+        keep = keep[np.argsort(slots[keep], kind="stable")]
         slots, nrows, e16, bias = slots[keep], nrows[keep], e16[keep], bias[keep]
         nt = (nrows + MT_TILE - 1) // MT_TILE
         T = int(nt.sum())
@@ -1094,8 +1100,12 @@ def mt_topk(tiles: MtTiles, Q: torch.Tensor, k: int, p_e32: torch.Tensor, p_bias
     sampled lower bound of the 2k-th best, the best 2k (<= 16) of them
     re-scored in fp32 from the tenants' rows. Returns (scores fp32 [nq, k],
     keys int64 [nq, k] = slot << 32 | row, overflow int32 [nq]): a query
-    whose candidate list overflowed (ovf = 1) must be recomputed by the
-    caller; rows that are not live nodes come back as (-inf, -1)."""
+    whose candidate list overflowed, or one of whose k best stored rows is not
+    a live node (ovf = 1), must be recomputed by the caller: such a row comes
+    back as (-inf, -1) in place, where the per-tenant searches -- which drop it
+    inside its tenant and merge -- would return the next node of another
+    tenant. Without such a row the k best stored rows are nodes and lie in
+    their tenants' own top-k, so both routes return them."""
     L = _lib.lib()
     dev = Q.device
     nq, D = Q.shape
@@ -1138,5 +1148,6 @@ def mt_topk(tiles: MtTiles, Q: torch.Tensor, k: int, p_e32: torch.Tensor, p_bias
     key = torch.empty((nq, k), dtype=torch.long, device=dev)
     _lib.check(L.lzk_mt_rerank(Qf.data_ptr(), D, D, oi.data_ptr(), kc, nq, int(k), tiles.slot.data_ptr(),
                                tiles.row0.data_ptr(), p_e32.data_ptr(), p_bias.data_ptr(), p_kind.data_ptr(),
-                               0 if metric == "l2" else 1, s.data_ptr(), key.data_ptr(), st), "lzk_mt_rerank")
+                               0 if metric == "l2" else 1, s.data_ptr(), key.data_ptr(), ovf.data_ptr(), st),
+               "lzk_mt_rerank")
     return s, key, ovf

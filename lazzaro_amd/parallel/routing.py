@@ -593,8 +593,9 @@ def _global_small(svc, gd, Qall: torch.Tensor, limit: int, me: int, dev):
     """Every query against every small tenant of the global directory
     (:meth:`DistributedMemoryService.global_directory`) in one tile-table
     pass. Returns (scores, keys = rank << 56 | slot << 32 | row, tenant keys,
-    the queries whose candidate list overflowed -- None when none did -- to be
-    redone by the per-tenant path; those queries' rows here are empty)."""
+    the queries whose candidate list overflowed or whose k best stored rows
+    include a removed (ghost) row -- None when there is none -- to be redone by
+    the per-tenant path; those queries' rows here are empty)."""
     from ..ops.search import mt_topk
     table = gd["table"]
     locks = [svc.systems[u]._graph_lock for u in gd["small"]] if gd["lock"] else []
@@ -618,7 +619,7 @@ def _global_small(svc, gd, Qall: torch.Tensor, limit: int, me: int, dev):
     tk = torch.where(ok, gd["tkeys"][(key >> 32).clamp_min(0)], torch.full_like(key, -1))
     key = torch.where(ok, (me << 56) | key, torch.full_like(key, -1))
     redo = None
-    if bool((ovf != 0).any()):  # rare: pathological score distributions
+    if bool((ovf != 0).any()):  # rare: pathological score distributions, a ghost among a query's nearest rows
         redo = torch.nonzero(ovf != 0).flatten()
         s[redo] = float("-inf")
         key[redo] = -1

@@ -376,7 +376,10 @@ class DistributedMemoryService:
         mutated tenant's class changed; a mutated small tenant only has its
         table entry refreshed -- no per-call pass over thousands of tenants."""
         d = self._gdir
-        if d is not None and d["D"] == D and d["k"] >= k and d["membership"] == self._membership:
+        # (the classes depend on routing.MT_GLOBAL: a directory built under the
+        # other setting would keep serving the route that was switched off)
+        if d is not None and d["D"] == D and d["k"] >= k and d["membership"] == self._membership \
+                and d["mt"] == routing.MT_GLOBAL:
             if self._gdir_dirty:
                 dirty, self._gdir_dirty = self._gdir_dirty, set()
                 for u in dirty:
@@ -414,7 +417,8 @@ class DistributedMemoryService:
                 st = getattr(self.systems[u].graph, "stream", None)
                 if st is not None:
                     streams[st.cuda_stream] = st
-        self._gdir = {"D": D, "k": k, "membership": self._membership, "cls": cls, "small": small,
+        self._gdir = {"D": D, "k": k, "membership": self._membership, "mt": routing.MT_GLOBAL, "cls": cls,
+                      "small": small,
                       "slots": np.asarray(slots, np.int64), "tkeys": tkdev, "big": big, "table": table,
                       "streams": list(streams.values()),
                       "lock": any(getattr(self.systems[u], "enable_async", False) for u in small)}

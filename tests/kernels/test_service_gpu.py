@@ -247,3 +247,100 @@ def test_search_global_multi_tenant_pass_matches_per_tenant(tmp_path, monkeypatc
     assert torch.equal(grow, wrow)
     assert (want.keys >= 0).all()
     svc.close()
+
+
+def test_search_global_routes_agree_with_ghosts_and_unsorted_slots(tmp_path, monkeypatch):
+    """The three routes of search_global_batch -- the tile-table pass
+    (MT_GLOBAL = True), the per-tenant store searches (MT_GLOBAL = False) and
+    the tile-table pass whose every list overflows and is redone per tenant --
+    return the hits of tests/kernels/_mt_ref.py ``global_ref``, computed on the
+    host from the graphs' columns: per tenant the top-k of its stored rows, the
+    non-nodes dropped, the rest merged by (score desc, key asc).
+
+    The tenants of the test above, with what it leaves out: rows removed with
+    ``unstore=False`` (ghosts that stay in the store; tile rows 0 and 64, which
+    the threshold sample reads, among them) next to unstored ones, queries
+    placed on ghosts -- the ghost is then the global nearest stored row, which
+    must not cost the query a hit --, the same vector stored in several tenants
+    (exact ties across tenants, broken by key) and table slots that do not
+    ascend in directory order (two late tenants are entered into the tenant
+    table first). The big tenant is big by a lowered BIG_ROWS, which keeps the
+    host reference small."""
+    from lazzaro_amd.ops import search as S
+    from lazzaro_amd.parallel import routing
+    from tests.kernels import _mt_ref as R
+    emb = RandEmbedder()
+    k = 6
+    monkeypatch.setattr(routing, "BIG_ROWS", 2048)
+    users = [f"g{i}" for i in range(40)]
+    svc = _seeded_service(tmp_path, emb, [])
+    rng = np.random.default_rng(9)
+    torch.manual_seed(9)
+    # (entries in {0, +-1/4, +-1/2}: every kernel scores these rows exactly, so their copies tie bit for bit)
+    shared = torch.randint(-2, 3, (3, 64), device="cuda").float() / 4
+    ghosts = []
+    for j, u in enumerate(users):
+        g = svc.system(u).graph
+        n = 1 if j % 13 == 0 else int(rng.integers(2, 700))
+        V = torch.nn.functional.normalize(torch.randn(n, 64, device="cuda"), dim=1)
+        if n > 20 and j % 3 == 0:
+            V[10:13] = shared  # the same three vectors in a dozen tenants
+        g.add_nodes([f"{u}_{i}" for i in range(n)], [f"{u} {i}" for i in range(n)], V, shard=g.shard_id("work"),
+                    stored=True)
+        if n > 20:
+            gone = ([0, 64] if n > 64 else [0]) + ([11] if j % 6 == 0 else [])  # (11: a ghost that ties with live copies)
+            g.remove_nodes(gone, unstore=False)
+            g.remove_nodes([3, 7, n - 1], unstore=True)
+            ghosts += [V[r] for r in gone]
+    big = svc.system("big").graph
+    n = routing.BIG_ROWS + 500
+    big.add_nodes([f"big_{i}" for i in range(n)], [f"big {i}" for i in range(n)],
+                  torch.nn.functional.normalize(torch.randn(n, 64, device="cuda"), dim=1), shard=big.shard_id("work"),
+                  stored=True)
+    big.remove_nodes([0, 5], unstore=False)
+    # two late tenants take the first table slots: the directory's slot column is not ascending
+    table = svc.tenant_table(svc.systems[users[0]].graph.device)
+    table.slots_host([users[35], users[20]], svc.systems)
+    Q = torch.nn.functional.normalize(torch.randn(300, 64, device="cuda"), dim=1)
+    G = torch.stack(ghosts)
+    Q[:80] = G[torch.arange(80, device="cuda") % G.shape[0]]
+    Q[40:80] = torch.nn.functional.normalize(Q[40:80] + 0.02 * torch.randn(40, 64, device="cuda"), dim=1)
+    Q[80:83] = shared
+    res = {}
+    for name, mt, ovf in (("tiles", True, False), ("per tenant", False, False), ("tiles, overflow", True, True)):
+        with monkeypatch.context() as m:
+            m.setattr(routing, "MT_GLOBAL", mt)
+            if ovf:
+                m.setattr(S, "_mt_threshold", lambda Xs, bs, Q16, *a: torch.full(
+                    (Q16.shape[0],), float("-inf"), device=Q16.device))
+            res[name] = routing.search_global_batch(svc, Q, k)
+            gd = svc.global_directory(64, k)
+            assert (len(gd["small"]) == 40) == mt and len(gd["big"]) == (1 if mt else 41)
+            if mt:
+                sl = gd["slots"].tolist()
+                assert sl != sorted(sl)
+    torch.cuda.synchronize()
+    # the reference, from the graphs' own columns
+    tenants, tkey = [], {}
+    for u, ms in svc.systems.items():
+        g = ms.graph
+        with g.on_stream():
+            X = g.emb32[: g.n].float().cpu().numpy()
+            b = g.store_bias("l2")[: g.n].cpu().numpy()
+        slot = table.slot[u]
+        tkey[slot] = routing.tenant_key(u)
+        tenants.append(R.Tenant(slot, X, b, np.asarray(g.mirror("kind"), dtype=np.uint8)))
+    tab = R.Table(tenants)
+    assert int(tab.stored[tab.slot != table.slot["big"]].sum()) > 8192  # (the overflow variant does overflow)
+    assert int((tab.stored & (tab.kind != R.NODE)).sum()) > 40
+    eS, eK, eB = tab.global_ref(Q.cpu().numpy(), k, "l2")
+    assert (eK >= 0).all()
+    eT = np.vectorize(tkey.get)(eK >> 32)
+    for name, hits in res.items():
+        keys = hits.keys.cpu().numpy()
+        assert (keys >= 0).all(), name  # k live stored nodes exist: every query gets k hits
+        bad = np.nonzero((keys != eK).any(1))[0]
+        assert bad.size == 0, (name, bad[:10].tolist(), keys[bad[:2]].tolist(), eK[bad[:2]].tolist())
+        assert np.array_equal(hits.tenant_keys.cpu().numpy(), eT), name
+        assert (np.abs(hits.scores.cpu().numpy().astype(np.float64) - eS) <= eB).all(), name
+    svc.close()

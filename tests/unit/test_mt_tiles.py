@@ -25,6 +25,10 @@ def test_tile_table_covers_every_row_once():
             assert (s, r) not in seen
             seen[(s, r)] = i
     assert len(seen) == int(nrows.sum())
+    # tiles ascend by (slot, row0) whatever the order of ``slots``: candidate id
+    # (tile * 256 + row in tile) order is result key (slot << 32 | row) order
+    order = [(int(t.slot[i]), int(t.row0[i])) for i in range(t.n_tiles)]
+    assert order == sorted(order) and [s for s, _ in order] == [0, 3, 5, 5, 5, 5, 7, 7]
     want = sum(-(-int(t.n[i]) // MT_STRIDE) for i in range(t.n_tiles))
     assert t.n_sample == want
     for ti, r in zip(t.s_tile.tolist(), t.s_row.tolist()):
