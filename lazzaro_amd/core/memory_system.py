@@ -344,7 +344,10 @@ class MemorySystem(ConsolidationMixin):
         fault_point("provider.llm")
         return self.llm.completion(messages, response_format)
 
-    def _search_batch(self, embs, k: int, where=None) -> List[List[str]]:
+    def _search_batch(self, embs, k: int, where=None, mmr=None) -> List[List[str]]:
+        if mmr is not None:  # (where= only when set, as below: the store sees the kwargs a caller gave)
+            kw = dict(mmr) if where is None else dict(mmr, where=where)
+            return self.vector_store.search_nodes_batch(embs, user_id=self.user_id, limit=k, **kw)
         if where is not None:
             return self.vector_store.search_nodes_batch(embs, user_id=self.user_id, limit=k, where=where)
         fn = getattr(self.vector_store, "search_nodes_batch", None)
@@ -617,32 +620,57 @@ class MemorySystem(ConsolidationMixin):
             raise NotImplementedError("a filtered search (where=) needs a store bound to the tenant graph (HBMStore)")
         return flt
 
-    def search_memories(self, query: str, limit: int = 5, where=None) -> List[Node]:
+    def _mmr(self, limit, diversity, fetch_k):
+        """``diversity`` / ``fetch_k`` of a search as the kwargs the store is
+        given (None: a plain search), validated before any work (the
+        selection compares the bound tenant graph's fp32 rows; a store that
+        holds its own rows has none)."""
+        if diversity is None and fetch_k is None:
+            return None
+        from ..ops.mmr_ops import pool_size
+        pool_size(limit, diversity, fetch_k)
+        if not self._store_binds_graph():
+            raise NotImplementedError(
+                "a diverse search (diversity=) needs a store bound to the tenant graph (HBMStore)")
+        return {"diversity": float(diversity), "fetch_k": fetch_k}
+
+    def search_memories(self, query: str, limit: int = 5, where=None, diversity=None, fetch_k=None) -> List[Node]:
         """``where`` (a :class:`MemoryFilter` or a dict of its fields): only
         the memories passing it are searched -- the ``limit`` nearest AMONG
-        them, not a post-filter of the nearest."""
+        them, not a post-filter of the nearest. ``diversity`` (0 .. 1): the
+        results are picked from the ``fetch_k`` nearest (default
+        ``max(16, 2 limit)``, at most 64) by maximal marginal relevance --
+        each pick trades cosine closeness to the query against cosine
+        similarity to the picks before it -- and come back in pick order."""
         if where is not None:
             where = self._where(where)
+        mmr = self._mmr(limit, diversity, fetch_k)
         with tracer.stage("embed_query", self._device):
             q = self._get_embedding(query)
         with self._graph_lock:
             with tracer.stage("search", self._device):
-                if where is None:
+                if mmr is not None:
+                    kw = mmr if where is None else dict(mmr, where=where)
+                    ids = self.vector_store.search_nodes(q, user_id=self.user_id, limit=limit, **kw)
+                elif where is None:
                     ids = self.vector_store.search_nodes(q, user_id=self.user_id, limit=limit)
                 else:
                     ids = self.vector_store.search_nodes(q, user_id=self.user_id, limit=limit, where=where)
             return [n for n in (self.buffer.get_node(i) for i in ids) if n is not None]
 
-    def search_memories_batch(self, queries: List[str], limit: int = 5, where=None) -> List[List[Node]]:
+    def search_memories_batch(self, queries: List[str], limit: int = 5, where=None, diversity=None,
+                              fetch_k=None) -> List[List[Node]]:
         """Batched ``search_memories`` (reference :1460-1472 per query): one
         embedding call (a device tensor when the encoder is on-device), one
         store search -- the fused MFMA candidate scan plus an fp32 re-rank
-        over the tenant's HBM rows -- and one row -> Node mapping. ``where``:
-        one filter for the whole batch (see :meth:`search_memories`)."""
+        over the tenant's HBM rows -- and one row -> Node mapping. ``where``,
+        ``diversity``, ``fetch_k``: one setting for the whole batch (see
+        :meth:`search_memories`)."""
         if where is not None:
             where = self._where(where)
+        mmr = self._mmr(limit, diversity, fetch_k)
         t0 = time.perf_counter()
-        out = self._search_finish(self._search_submit(queries, limit, where))
+        out = self._search_finish(self._search_submit(queries, limit, where, mmr))
         self._count_search(len(out), (time.perf_counter() - t0) * 1e3)
         return out
 
@@ -652,24 +680,27 @@ class MemorySystem(ConsolidationMixin):
         m["search_batches"] = m.get("search_batches", 0) + 1
         m["search_ms"] = m.get("search_ms", 0.0) + ms
 
-    def search_memories_stream(self, batches: Iterable[List[str]], limit: int = 5, where=None):
+    def search_memories_stream(self, batches: Iterable[List[str]], limit: int = 5, where=None, diversity=None,
+                               fetch_k=None):
         """Pipelined ``search_memories_batch`` for serving loops: batches i+1 ..
         i+STREAM_DEPTH are tokenised and their embed + scan enqueued on the
         device BEFORE the host waits for batch i and maps its rows to Nodes,
         so host work (tokenizer, result mapping) hides under device work.
         Yields one result list per input batch, in order; results equal
-        ``search_memories_batch``. ``where``: one filter for all batches."""
+        ``search_memories_batch``. ``where``, ``diversity``, ``fetch_k``: one
+        setting for all batches."""
         if where is not None:
             where = self._where(where)
+        mmr = self._mmr(limit, diversity, fetch_k)
         pending = collections.deque()
         for qs in batches:
-            pending.append(self._search_submit(qs, limit, where))
+            pending.append(self._search_submit(qs, limit, where, mmr))
             if len(pending) > STREAM_DEPTH:
                 yield self._search_finish(pending.popleft())
         while pending:
             yield self._search_finish(pending.popleft())
 
-    def _search_submit(self, queries, limit: int, where=None):
+    def _search_submit(self, queries, limit: int, where=None, mmr=None):
         """Enqueue embed + store search; returns a handle for _search_finish.
         With the graph-bound store the result rows stay on the device and come
         back with one async copy into pinned memory (no host sync here)."""
@@ -696,7 +727,10 @@ class MemorySystem(ConsolidationMixin):
                         # rows the graph does not hold as nodes are skipped (reference
                         # :1467-1472): marked on the device (by the re-rank kernel), so
                         # mapping needs no mirror
-                        if where is None:
+                        if mmr is not None:  # (the pool search marks non-node rows: they take no pick)
+                            _, rows = g.store_search(embs, int(limit), getattr(self.store, "metric", "l2"),
+                                                     node_rows=True, where=where, **mmr)
+                        elif where is None:
                             _, rows = g.store_search(embs, int(limit), getattr(self.store, "metric", "l2"),
                                                      node_rows=True)
                         else:  # (every row a filtered search returns is a node)
@@ -712,7 +746,7 @@ class MemorySystem(ConsolidationMixin):
                         return ("rows_dev", g, rows, ev, g.row_epoch)
                     return ("rows", g, rows, None, g.row_epoch)
         with tracer.stage("search", self._device):
-            return ("ids", None, self._search_batch(embs, limit, where), None, 0)
+            return ("ids", None, self._search_batch(embs, limit, where, mmr), None, 0)
 
     def _search_finish(self, h) -> List[List[Node]]:
         kind_, g0, data, ev, epoch = h  # (the row epoch searched under: a compaction may run before the finish)
@@ -787,7 +821,8 @@ class MemorySystem(ConsolidationMixin):
                 "rows_reclaimed_total": g.rows_reclaimed_total, "ann_removed": g.ann_removed,
                 "ann_upserts": g.ann_upserts, "ann_rebuilds": g.ann_rebuilds,
                 "filtered_searches": g.filtered_searches, "filter_plans_built": g.filter_plans_built,
-                "filtered_sparse": g.filtered_sparse, "filtered_ann": g.filtered_ann, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
+                "filtered_sparse": g.filtered_sparse, "filtered_ann": g.filtered_ann,
+                "mmr_searches": g.mmr_searches, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
                 "avg_search_batch_ms": round(sms / m["search_batches"], 3) if m.get("search_batches") else 0.0}
 
     def _graph_bytes(self) -> int:

@@ -105,9 +105,12 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
                  min_salience: Optional[float] = None, max_salience: Optional[float] = None,
                  since: Optional[float] = None, until: Optional[float] = None,
                  accessed_since: Optional[float] = None, min_access_count: Optional[int] = None,
-                 super_nodes: Optional[bool] = None, exclude_ids: Optional[str] = None):
+                 super_nodes: Optional[bool] = None, exclude_ids: Optional[str] = None,
+                 diversity: Optional[float] = None, fetch_k: Optional[int] = None):
     """``MemoryFilter`` fields as optional query parameters (the set-valued
-    ones comma separated); none given: the unfiltered search."""
+    ones comma separated); none given: the unfiltered search. ``diversity``
+    (0 .. 1) and ``fetch_k``: results picked for diversity from the
+    ``fetch_k`` nearest (``MemorySystem.search_memories``)."""
     if not _ms:
         return []
     where = {k: v for k, v in (("types", _csv(types)), ("shard_keys", _csv(shard_keys)),
@@ -115,7 +118,10 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
                                ("until", until), ("accessed_since", accessed_since),
                                ("min_access_count", min_access_count), ("super_nodes", super_nodes),
                                ("exclude_ids", _csv(exclude_ids))) if v is not None}
-    hits = _ms.search_memories(q, limit=limit, where=where) if where else _ms.search_memories(q, limit=limit)
+    kw = {"where": where} if where else {}
+    if diversity is not None or fetch_k is not None:
+        kw.update(diversity=diversity, fetch_k=fetch_k)
+    hits = _ms.search_memories(q, limit=limit, **kw)
     return [{"id": n.id, "content": n.content, "salience": n.salience, "shard": n.shard_key} for n in hits]
 
 

@@ -2455,7 +2455,8 @@ class TenantGraph:
         self._bias_cache[metric] = (self._store_version, b)
         return b
 
-    def store_search(self, Q: torch.Tensor, k: int, metric: str = "l2", node_rows: bool = False, where=None):
+    def store_search(self, Q: torch.Tensor, k: int, metric: str = "l2", node_rows: bool = False, where=None,
+                     diversity: Optional[float] = None, fetch_k: Optional[int] = None):
         """The store's vector search over this tenant (reference
         ``LanceDBStore.search_nodes``: flat scan, L2 unless told otherwise,
         vector_store.py:132-140). fp32 scores -- -|q-x|^2 for L2, cosine, or
@@ -2465,7 +2466,12 @@ class TenantGraph:
         memory_system.py:1467-1472) -- inside the re-rank kernel when it runs.
         ``where`` (a ``core.filters.MemoryFilter`` or a dict of its fields):
         only graph nodes in the store that pass it are searched (every result
-        row is a node, so ``node_rows`` changes nothing then)."""
+        row is a node, so ``node_rows`` changes nothing then).
+        ``diversity`` (0 .. 1): the ``k`` results are picked from the
+        ``fetch_k`` nearest by greedy maximal marginal relevance and come
+        back in pick order (:meth:`_store_search_mmr`)."""
+        if diversity is not None or fetch_k is not None:
+            return self._store_search_mmr(Q, k, metric, node_rows, where, diversity, fetch_k)
         if where is not None:
             with self.on_stream():
                 return self._store_search_where(Q, k, metric, where)
@@ -2477,6 +2483,35 @@ class TenantGraph:
             return s, r
 
     _nodes_marked = False  # the last _store_search already marked non-node rows (re-rank kernel)
+
+    mmr_searches = 0
+
+    def _store_search_mmr(self, Q, k, metric, node_rows, where, diversity, fetch_k):
+        """:meth:`store_search` with ``diversity``: the pool is the plain
+        search at ``k = fetch_k`` (default ``max(16, 2 k)``, at most
+        MAX_FETCH_K = 64) by whatever route that takes, ``node_rows`` and
+        ``where`` passed through; rows it marked -1 are not candidates. The
+        ``k`` picks are greedy maximal marginal relevance over the pool's
+        fp32 rows (ops.mmr_ops.mmr_select: cosine relevance and cosine
+        redundancy whatever the metric, ties to the lower row), returned in
+        pick order with the pool's own scores gathered, (-inf, -1) once the
+        pool ran out. No host synchronisation of its own."""
+        from ..ops.mmr_ops import mmr_select, pool_size
+        k = int(k)
+        F = pool_size(k, diversity, fetch_k)
+        s, r = self.store_search(Q, F, metric, node_rows, where)
+        self.mmr_searches += 1
+        with self.on_stream():
+            Qf = Q.to(self.device, torch.float32)
+            if Qf.dim() == 1:
+                Qf = Qf[None, :]
+            if self.n == 0 or self.dim is None or Qf.shape[1] != self.dim:
+                return s[:, :k], r[:, :k]  # (nothing was searched: all padding)
+            pick, _ = mmr_select(self.emb32[: self.n], Qf, r, k, float(diversity))
+            ok = pick >= 0
+            p = pick.long().clamp_min(0)
+            return (torch.where(ok, torch.gather(s, 1, p), torch.full_like(s[:, :k], NEG_INF)),
+                    torch.where(ok, torch.gather(r, 1, p), torch.full_like(r[:, :k], -1)))
 
     # ---- filtered search: state (class defaults; the containers are made on first use)
     _meta_gen = 0  # bumps on a scalar column write that bumps no other counter (set_scalar)
@@ -2892,8 +2927,12 @@ class TenantGraph:
         o = torch.sort(s, dim=1, descending=True, stable=True).indices[:, :k]
         return self._pad_k(torch.gather(s, 1, o), torch.gather(cand, 1, o), k)
 
-    def search_ids(self, Q, k: int, metric: str = "l2", where=None) -> List[List[str]]:
-        _, r = self.store_search(Q, k, metric, where=where)
+    def search_ids(self, Q, k: int, metric: str = "l2", where=None, diversity=None, fetch_k=None) -> List[List[str]]:
+        if diversity is not None or fetch_k is not None:
+            # (node rows only: a row the caller would drop must not take a pick)
+            _, r = self.store_search(Q, k, metric, node_rows=True, where=where, diversity=diversity, fetch_k=fetch_k)
+        else:
+            _, r = self.store_search(Q, k, metric, where=where)
         ids = self.ids
         return [[ids[x] for x in row if x >= 0] for row in r.cpu().tolist()]
 

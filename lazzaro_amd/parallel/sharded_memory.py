@@ -570,7 +570,8 @@ class ShardedMemorySystem:
             out.append((s, meta))
         return out
 
-    def search_memories_batch(self, queries: Sequence[str], limit: int = 5, where=None) -> List[List[Dict]]:
+    def search_memories_batch(self, queries: Sequence[str], limit: int = 5, where=None, diversity=None,
+                              fetch_k=None) -> List[List[Dict]]:
         """Collective ``search_memories`` over the whole tenant (reference
         :1460-1472): every rank embeds its own queries, the query rows are
         all-gathered, each rank runs the store search (fused scan + fp32
@@ -579,6 +580,8 @@ class ShardedMemorySystem:
         to the rank that asked. Returns this rank's results."""
         if where is not None:
             raise NotImplementedError("ShardedMemorySystem.search_memories_batch takes no filter (where=)")
+        if diversity is not None or fetch_k is not None:
+            raise NotImplementedError("ShardedMemorySystem.search_memories_batch does not select by diversity")
 
         g = self.g
         dev = self.device
