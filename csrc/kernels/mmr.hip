@@ -30,6 +30,7 @@
 // rows get bit-identical dots, norms and objectives, so the row decides
 // between them. A launch takes one path for every dot it computes.
 #include "lzk_common.h"
+#include "lzk_dot16.h"  // lzk_dot16_part, lzk_fold16, lzk_cos: the layout stated above
 
 namespace {
 
@@ -37,44 +38,6 @@ constexpr int MMR_NT = 256;
 constexpr int MMR_MAX_F = 64;           // one pool slot per lane of the selecting wave
 constexpr int MMR_NONE = 0x7fffffff;    // tie key of an empty slot: loses to every row
 constexpr size_t MMR_MAX_LDS = 64 * 1024;
-
-// this lane's share of <a, x> and of |x|^2 (a: LDS, zero padded to a multiple of 4; x: a pool row)
-__device__ __forceinline__ void mmr_dot_part(const float* a, const float* __restrict__ x, int D, int vec, int part,
-                                             float& dot, float& xx) {
-  dot = 0.f;
-  xx = 0.f;
-  if (vec) {
-    const int n4 = D >> 2;
-#pragma unroll 4
-    for (int d4 = part; d4 < n4; d4 += 16) {
-      const float4 xv = *reinterpret_cast<const float4*>(x + 4 * d4);
-      const float4 av = *reinterpret_cast<const float4*>(a + 4 * d4);
-      dot = fmaf(av.x, xv.x, dot); xx = fmaf(xv.x, xv.x, xx);
-      dot = fmaf(av.y, xv.y, dot); xx = fmaf(xv.y, xv.y, xx);
-      dot = fmaf(av.z, xv.z, dot); xx = fmaf(xv.z, xv.z, xx);
-      dot = fmaf(av.w, xv.w, dot); xx = fmaf(xv.w, xv.w, xx);
-    }
-  } else {
-    for (int d = part; d < D; d += 16) {
-      const float xv = x[d];
-      dot = fmaf(a[d], xv, dot);
-      xx = fmaf(xv, xv, xx);
-    }
-  }
-}
-
-// the 16 partial sums of a group, in the one fixed order
-__device__ __forceinline__ float mmr_fold16(float a) {
-  a += __shfl_xor(a, 8, 64);
-  a += __shfl_xor(a, 4, 64);
-  a += __shfl_xor(a, 2, 64);
-  a += __shfl_xor(a, 1, 64);
-  return a;
-}
-
-__device__ __forceinline__ float mmr_cos(float dot, float na, float nb) {
-  return (na > 0.f && nb > 0.f) ? dot / (na * nb) : 0.f;
-}
 
 __global__ __launch_bounds__(MMR_NT) void mmr_select_kernel(
     const float* __restrict__ X, long ldx, int n, const float* __restrict__ Q, long ldq, int D,
@@ -113,7 +76,7 @@ __global__ __launch_bounds__(MMR_NT) void mmr_select_kernel(
     } else {
       for (int d = part; d < D; d += 16) qq = fmaf(s_q[d], s_q[d], qq);
     }
-    qn = sqrtf(mmr_fold16(qq));
+    qn = sqrtf(lzk_fold16(qq));
   }
 
   // ---- relevance and norms of the owned slots
@@ -121,13 +84,13 @@ __global__ __launch_bounds__(MMR_NT) void mmr_select_kernel(
     const int f = f0 + grp;
     const int r = f < F ? s_row[f] : -1;
     float dot = 0.f, xx = 0.f;
-    if (r >= 0) mmr_dot_part(s_q, X + (long)r * ldx, D, vec, part, dot, xx);
-    dot = mmr_fold16(dot);
-    xx = mmr_fold16(xx);
+    if (r >= 0) lzk_dot16_part(s_q, X + (long)r * ldx, D, vec, part, dot, xx);
+    dot = lzk_fold16(dot);
+    xx = lzk_fold16(xx);
     if (part == 0 && f < F) {
       const float xn = sqrtf(xx);
       s_nrm[f] = xn;
-      s_rel[f] = mmr_cos(dot, qn, xn);
+      s_rel[f] = lzk_cos(dot, qn, xn);
     }
   }
   __syncthreads();
@@ -186,9 +149,9 @@ __global__ __launch_bounds__(MMR_NT) void mmr_select_kernel(
       const int f = f0 + grp;
       const int r = f < F ? s_row[f] : -1;
       float dot = 0.f, xx = 0.f;
-      if (r >= 0) mmr_dot_part(s_p, X + (long)r * ldx, D, vec, part, dot, xx);
-      dot = mmr_fold16(dot);
-      if (part == 0 && r >= 0) s_max[f] = fmaxf(s_max[f], mmr_cos(dot, s_nrm[f], pn));
+      if (r >= 0) lzk_dot16_part(s_p, X + (long)r * ldx, D, vec, part, dot, xx);
+      dot = lzk_fold16(dot);
+      if (part == 0 && r >= 0) s_max[f] = fmaxf(s_max[f], lzk_cos(dot, s_nrm[f], pn));
     }
     __syncthreads();
   }

@@ -620,31 +620,46 @@ class MemorySystem(ConsolidationMixin):
             raise NotImplementedError("a filtered search (where=) needs a store bound to the tenant graph (HBMStore)")
         return flt
 
-    def _mmr(self, limit, diversity, fetch_k):
-        """``diversity`` / ``fetch_k`` of a search as the kwargs the store is
-        given (None: a plain search), validated before any work (the
-        selection compares the bound tenant graph's fp32 rows; a store that
-        holds its own rows has none)."""
-        if diversity is None and fetch_k is None:
+    def _mmr(self, limit, diversity, fetch_k, expand=None):
+        """``diversity`` / ``fetch_k`` / ``expand`` of a search as the kwargs
+        the store is given (None: a plain search), validated before any work
+        (both selections read the bound tenant graph's fp32 rows, the
+        expansion its links; a store that holds its own rows has neither)."""
+        if diversity is None and fetch_k is None and expand is None:
             return None
-        from ..ops.mmr_ops import pool_size
-        pool_size(limit, diversity, fetch_k)
+        kw = {}
+        if diversity is not None or fetch_k is not None:
+            from ..ops.mmr_ops import pool_size
+            pool_size(limit, diversity, fetch_k)
+            kw.update(diversity=float(diversity), fetch_k=fetch_k)
+        if expand is not None:
+            from ..ops.expand_ops import pool_bound
+            from .expand import GraphExpand
+            expand = GraphExpand.coerce(expand)
+            pool_bound(expand, limit if not kw else None)  # (with diversity= the expansion returns the pool)
+            kw.update(expand=expand)
         if not self._store_binds_graph():
             raise NotImplementedError(
-                "a diverse search (diversity=) needs a store bound to the tenant graph (HBMStore)")
-        return {"diversity": float(diversity), "fetch_k": fetch_k}
+                ("a diverse search (diversity=)" if "diversity" in kw else "an expanded search (expand=)")
+                + " needs a store bound to the tenant graph (HBMStore)")
+        return kw
 
-    def search_memories(self, query: str, limit: int = 5, where=None, diversity=None, fetch_k=None) -> List[Node]:
+    def search_memories(self, query: str, limit: int = 5, where=None, diversity=None, fetch_k=None,
+                        expand=None) -> List[Node]:
         """``where`` (a :class:`MemoryFilter` or a dict of its fields): only
         the memories passing it are searched -- the ``limit`` nearest AMONG
         them, not a post-filter of the nearest. ``diversity`` (0 .. 1): the
         results are picked from the ``fetch_k`` nearest (default
         ``max(16, 2 limit)``, at most 64) by maximal marginal relevance --
         each pick trades cosine closeness to the query against cosine
-        similarity to the picks before it -- and come back in pick order."""
+        similarity to the picks before it -- and come back in pick order.
+        ``expand`` (an int hop count, a dict or a :class:`GraphExpand`): the
+        links of the nearest memories are followed and the ``limit`` best of
+        everything reached come back, scored by closeness blended with the
+        activation their links carried (core/expand.py)."""
         if where is not None:
             where = self._where(where)
-        mmr = self._mmr(limit, diversity, fetch_k)
+        mmr = self._mmr(limit, diversity, fetch_k, expand)
         with tracer.stage("embed_query", self._device):
             q = self._get_embedding(query)
         with self._graph_lock:
@@ -659,16 +674,16 @@ class MemorySystem(ConsolidationMixin):
             return [n for n in (self.buffer.get_node(i) for i in ids) if n is not None]
 
     def search_memories_batch(self, queries: List[str], limit: int = 5, where=None, diversity=None,
-                              fetch_k=None) -> List[List[Node]]:
+                              fetch_k=None, expand=None) -> List[List[Node]]:
         """Batched ``search_memories`` (reference :1460-1472 per query): one
         embedding call (a device tensor when the encoder is on-device), one
         store search -- the fused MFMA candidate scan plus an fp32 re-rank
         over the tenant's HBM rows -- and one row -> Node mapping. ``where``,
-        ``diversity``, ``fetch_k``: one setting for the whole batch (see
-        :meth:`search_memories`)."""
+        ``diversity``, ``fetch_k``, ``expand``: one setting for the whole
+        batch (see :meth:`search_memories`)."""
         if where is not None:
             where = self._where(where)
-        mmr = self._mmr(limit, diversity, fetch_k)
+        mmr = self._mmr(limit, diversity, fetch_k, expand)
         t0 = time.perf_counter()
         out = self._search_finish(self._search_submit(queries, limit, where, mmr))
         self._count_search(len(out), (time.perf_counter() - t0) * 1e3)
@@ -681,17 +696,17 @@ class MemorySystem(ConsolidationMixin):
         m["search_ms"] = m.get("search_ms", 0.0) + ms
 
     def search_memories_stream(self, batches: Iterable[List[str]], limit: int = 5, where=None, diversity=None,
-                               fetch_k=None):
+                               fetch_k=None, expand=None):
         """Pipelined ``search_memories_batch`` for serving loops: batches i+1 ..
         i+STREAM_DEPTH are tokenised and their embed + scan enqueued on the
         device BEFORE the host waits for batch i and maps its rows to Nodes,
         so host work (tokenizer, result mapping) hides under device work.
         Yields one result list per input batch, in order; results equal
-        ``search_memories_batch``. ``where``, ``diversity``, ``fetch_k``: one
-        setting for all batches."""
+        ``search_memories_batch``. ``where``, ``diversity``, ``fetch_k``,
+        ``expand``: one setting for all batches."""
         if where is not None:
             where = self._where(where)
-        mmr = self._mmr(limit, diversity, fetch_k)
+        mmr = self._mmr(limit, diversity, fetch_k, expand)
         pending = collections.deque()
         for qs in batches:
             pending.append(self._search_submit(qs, limit, where, mmr))
@@ -822,7 +837,7 @@ class MemorySystem(ConsolidationMixin):
                 "ann_upserts": g.ann_upserts, "ann_rebuilds": g.ann_rebuilds,
                 "filtered_searches": g.filtered_searches, "filter_plans_built": g.filter_plans_built,
                 "filtered_sparse": g.filtered_sparse, "filtered_ann": g.filtered_ann,
-                "mmr_searches": g.mmr_searches, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
+                "mmr_searches": g.mmr_searches, "expanded_searches": g.expanded_searches, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
                 "avg_search_batch_ms": round(sms / m["search_batches"], 3) if m.get("search_batches") else 0.0}
 
     def _graph_bytes(self) -> int:

@@ -106,11 +106,15 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
                  since: Optional[float] = None, until: Optional[float] = None,
                  accessed_since: Optional[float] = None, min_access_count: Optional[int] = None,
                  super_nodes: Optional[bool] = None, exclude_ids: Optional[str] = None,
-                 diversity: Optional[float] = None, fetch_k: Optional[int] = None):
+                 diversity: Optional[float] = None, fetch_k: Optional[int] = None,
+                 hops: Optional[int] = None, fanout: Optional[int] = None, graph_weight: Optional[float] = None):
     """``MemoryFilter`` fields as optional query parameters (the set-valued
     ones comma separated); none given: the unfiltered search. ``diversity``
     (0 .. 1) and ``fetch_k``: results picked for diversity from the
-    ``fetch_k`` nearest (``MemorySystem.search_memories``)."""
+    ``fetch_k`` nearest (``MemorySystem.search_memories``). ``hops``,
+    ``fanout``, ``graph_weight``: any of them given makes it an associative
+    search along the memories' links (``expand=``, core/expand.py; the others
+    keep their defaults)."""
     if not _ms:
         return []
     where = {k: v for k, v in (("types", _csv(types)), ("shard_keys", _csv(shard_keys)),
@@ -121,6 +125,9 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
     kw = {"where": where} if where else {}
     if diversity is not None or fetch_k is not None:
         kw.update(diversity=diversity, fetch_k=fetch_k)
+    expand = {k: v for k, v in (("hops", hops), ("fanout", fanout), ("graph_weight", graph_weight)) if v is not None}
+    if expand:
+        kw.update(expand=expand)
     hits = _ms.search_memories(q, limit=limit, **kw)
     return [{"id": n.id, "content": n.content, "salience": n.salience, "shard": n.shard_key} for n in hits]
 

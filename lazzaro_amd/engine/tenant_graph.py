@@ -2456,7 +2456,7 @@ class TenantGraph:
         return b
 
     def store_search(self, Q: torch.Tensor, k: int, metric: str = "l2", node_rows: bool = False, where=None,
-                     diversity: Optional[float] = None, fetch_k: Optional[int] = None):
+                     diversity: Optional[float] = None, fetch_k: Optional[int] = None, expand=None):
         """The store's vector search over this tenant (reference
         ``LanceDBStore.search_nodes``: flat scan, L2 unless told otherwise,
         vector_store.py:132-140). fp32 scores -- -|q-x|^2 for L2, cosine, or
@@ -2469,9 +2469,16 @@ class TenantGraph:
         row is a node, so ``node_rows`` changes nothing then).
         ``diversity`` (0 .. 1): the ``k`` results are picked from the
         ``fetch_k`` nearest by greedy maximal marginal relevance and come
-        back in pick order (:meth:`_store_search_mmr`)."""
+        back in pick order (:meth:`_store_search_mmr`).
+        ``expand`` (an int hop count, a dict or a ``core.expand.GraphExpand``):
+        the links of the nearest rows are walked and the ``k`` best of
+        everything reached come back with blended scores
+        (:meth:`store_search_expand`, which also returns ``via``; seeds and
+        targets are graph nodes, so ``node_rows`` changes nothing then)."""
         if diversity is not None or fetch_k is not None:
-            return self._store_search_mmr(Q, k, metric, node_rows, where, diversity, fetch_k)
+            return self._store_search_mmr(Q, k, metric, node_rows, where, diversity, fetch_k, expand)
+        if expand is not None:
+            return self.store_search_expand(Q, k, metric, where, expand)[:2]
         if where is not None:
             with self.on_stream():
                 return self._store_search_where(Q, k, metric, where)
@@ -2486,20 +2493,21 @@ class TenantGraph:
 
     mmr_searches = 0
 
-    def _store_search_mmr(self, Q, k, metric, node_rows, where, diversity, fetch_k):
+    def _store_search_mmr(self, Q, k, metric, node_rows, where, diversity, fetch_k, expand=None):
         """:meth:`store_search` with ``diversity``: the pool is the plain
         search at ``k = fetch_k`` (default ``max(16, 2 k)``, at most
         MAX_FETCH_K = 64) by whatever route that takes, ``node_rows`` and
-        ``where`` passed through; rows it marked -1 are not candidates. The
-        ``k`` picks are greedy maximal marginal relevance over the pool's
-        fp32 rows (ops.mmr_ops.mmr_select: cosine relevance and cosine
-        redundancy whatever the metric, ties to the lower row), returned in
-        pick order with the pool's own scores gathered, (-inf, -1) once the
-        pool ran out. No host synchronisation of its own."""
+        ``where`` passed through (with ``expand``, the expanded search at
+        ``k = fetch_k`` and its blended scores); rows it marked -1 are not
+        candidates. The ``k`` picks are greedy maximal marginal relevance
+        over the pool's fp32 rows (ops.mmr_ops.mmr_select: cosine relevance
+        and cosine redundancy whatever the metric, ties to the lower row),
+        returned in pick order with the pool's own scores gathered, (-inf,
+        -1) once the pool ran out. No host synchronisation of its own."""
         from ..ops.mmr_ops import mmr_select, pool_size
         k = int(k)
         F = pool_size(k, diversity, fetch_k)
-        s, r = self.store_search(Q, F, metric, node_rows, where)
+        s, r = self.store_search(Q, F, metric, node_rows, where, expand=expand)
         self.mmr_searches += 1
         with self.on_stream():
             Qf = Q.to(self.device, torch.float32)
@@ -2512,6 +2520,52 @@ class TenantGraph:
             p = pick.long().clamp_min(0)
             return (torch.where(ok, torch.gather(s, 1, p), torch.full_like(s[:, :k], NEG_INF)),
                     torch.where(ok, torch.gather(r, 1, p), torch.full_like(r[:, :k], -1)))
+
+    expanded_searches = 0
+
+    def store_search_expand(self, Q, k, metric: str = "l2", where=None, expand=1):
+        """:meth:`store_search` with ``expand``, returning (scores [M, k], rows
+        [M, k], via [M, k]). The seeds are the plain search at ``k = seed_k``
+        with ``node_rows=True`` by whatever route that takes, ``where`` passed
+        through; the visible-arc CSR (:meth:`csr`) is walked from them
+        (ops.expand_ops.expand_select holds the contract: ``hops`` Jacobi
+        hops, the first ``fanout`` arcs of weight ``>= min_weight`` per
+        source, max-product activation). Targets are graph nodes whose search
+        bias is finite -- ``store_bias``, or the filter plan's bias under
+        ``where``, so a row the filter rejects is never reached. Scores are
+        ``(1 - graph_weight) * cos + graph_weight * activation`` over the fp32
+        rows whatever the metric, descending, ties to the lower row, (-inf,
+        -1) beyond the candidate count. ``via``: -1 where the activation is
+        the row's own, else the row whose link carried it. The CSR is cached
+        per edge version; rebuilding it after an edge change synchronises
+        with the host. Nothing else here does."""
+        from ..core.expand import GraphExpand
+        from ..ops.expand_ops import expand_select, pool_bound
+        k = int(k)
+        sp = GraphExpand.coerce(expand)
+        pool_bound(sp, k)
+        _, seeds = self.store_search(Q, sp.seed_k, metric, True, where)
+        self.expanded_searches += 1
+        dev = self.device
+        Qf = Q.to(dev, torch.float32)
+        if Qf.dim() == 1:
+            Qf = Qf[None, :]
+        M = Qf.shape[0]
+        n = self.n
+        if n == 0 or self.dim is None or Qf.shape[1] != self.dim:  # (nothing was searched: all padding)
+            pad = torch.full((M, k), -1, dtype=torch.long, device=dev)
+            return torch.full((M, k), NEG_INF, device=dev), pad, pad.clone()
+        if where is not None:
+            from ..core.filters import MemoryFilter
+            with self.on_stream():
+                bias = self._filter_plan(MemoryFilter.coerce(where), metric == "l2").bias  # (the seed search's plan)
+        else:
+            bias = self.store_bias("l2" if metric == "l2" else "ip")
+        csr = self.csr()
+        with self.on_stream():
+            rows, scores, via, _ = expand_select(self.emb32[:n], Qf, seeds, csr, self.e["w"], self.kind, self.sup,
+                                                 bias, sp, k)
+        return scores, rows, via
 
     # ---- filtered search: state (class defaults; the containers are made on first use)
     _meta_gen = 0  # bumps on a scalar column write that bumps no other counter (set_scalar)
@@ -2927,10 +2981,12 @@ class TenantGraph:
         o = torch.sort(s, dim=1, descending=True, stable=True).indices[:, :k]
         return self._pad_k(torch.gather(s, 1, o), torch.gather(cand, 1, o), k)
 
-    def search_ids(self, Q, k: int, metric: str = "l2", where=None, diversity=None, fetch_k=None) -> List[List[str]]:
-        if diversity is not None or fetch_k is not None:
+    def search_ids(self, Q, k: int, metric: str = "l2", where=None, diversity=None, fetch_k=None,
+                   expand=None) -> List[List[str]]:
+        if diversity is not None or fetch_k is not None or expand is not None:
             # (node rows only: a row the caller would drop must not take a pick)
-            _, r = self.store_search(Q, k, metric, node_rows=True, where=where, diversity=diversity, fetch_k=fetch_k)
+            _, r = self.store_search(Q, k, metric, node_rows=True, where=where, diversity=diversity, fetch_k=fetch_k,
+                                     expand=expand)
         else:
             _, r = self.store_search(Q, k, metric, where=where)
         ids = self.ids
