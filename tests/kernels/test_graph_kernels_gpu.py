@@ -248,8 +248,10 @@ def test_ivfpq_fused_rerank_matches_library_path(monkeypatch, keep):
 @pytest.mark.parametrize("N,nq", [(37, 300), (4096, 1000), (1000, 70001)])
 def test_flat_top1_gpu(N, nq):
     """256x256 argmax kernel (k-means assign) vs an fp32 reference: partial row
-    and query tiles, negative best scores, exact duplicate rows (tie -> the
-    smaller row)."""
+    and query tiles, one exact duplicate row (the larger index never wins).
+    ``Q[:5] = -X[:5]`` makes one score of each of those queries negative, not
+    the best one: a negative best score, the packed key's sign branch and ties
+    across blocks are held by test_topk_stages_gpu.py (test_top1_*)."""
     from lazzaro_amd.ops.search import flat_top1
     g = torch.Generator().manual_seed(N + nq)
     D = 192
