@@ -620,14 +620,19 @@ class MemorySystem(ConsolidationMixin):
             raise NotImplementedError("a filtered search (where=) needs a store bound to the tenant graph (HBMStore)")
         return flt
 
-    def _mmr(self, limit, diversity, fetch_k, expand=None):
-        """``diversity`` / ``fetch_k`` / ``expand`` of a search as the kwargs
-        the store is given (None: a plain search), validated before any work
-        (both selections read the bound tenant graph's fp32 rows, the
-        expansion its links; a store that holds its own rows has neither)."""
-        if diversity is None and fetch_k is None and expand is None:
+    def _mmr(self, limit, diversity, fetch_k, expand=None, boost=None):
+        """``diversity`` / ``fetch_k`` / ``expand`` / ``boost`` of a search as
+        the kwargs the store is given (None: a plain search), validated before
+        any work (both selections read the bound tenant graph's fp32 rows, the
+        expansion its links, the boost its node columns; a store that holds
+        its own rows has none of them). A boost's ``now`` is fixed here: once
+        per call."""
+        if diversity is None and fetch_k is None and expand is None and boost is None:
             return None
         kw = {}
+        if boost is not None:
+            from .boost import MemoryBoost
+            kw.update(boost=MemoryBoost.coerce(boost).at())
         if diversity is not None or fetch_k is not None:
             from ..ops.mmr_ops import pool_size
             pool_size(limit, diversity, fetch_k)
@@ -640,12 +645,13 @@ class MemorySystem(ConsolidationMixin):
             kw.update(expand=expand)
         if not self._store_binds_graph():
             raise NotImplementedError(
-                ("a diverse search (diversity=)" if "diversity" in kw else "an expanded search (expand=)")
+                ("a diverse search (diversity=)" if "diversity" in kw else "an expanded search (expand=)"
+                 if "expand" in kw else "a boosted search (boost=)")
                 + " needs a store bound to the tenant graph (HBMStore)")
         return kw
 
     def search_memories(self, query: str, limit: int = 5, where=None, diversity=None, fetch_k=None,
-                        expand=None) -> List[Node]:
+                        expand=None, boost=None) -> List[Node]:
         """``where`` (a :class:`MemoryFilter` or a dict of its fields): only
         the memories passing it are searched -- the ``limit`` nearest AMONG
         them, not a post-filter of the nearest. ``diversity`` (0 .. 1): the
@@ -656,10 +662,13 @@ class MemorySystem(ConsolidationMixin):
         ``expand`` (an int hop count, a dict or a :class:`GraphExpand`): the
         links of the nearest memories are followed and the ``limit`` best of
         everything reached come back, scored by closeness blended with the
-        activation their links carried (core/expand.py)."""
+        activation their links carried (core/expand.py). ``boost`` (a number,
+        a dict or a :class:`MemoryBoost`): the ``limit`` best by closeness
+        PLUS a prior from each memory's salience, use and recency -- among
+        all memories, not a re-ordering of the nearest (core/boost.py)."""
         if where is not None:
             where = self._where(where)
-        mmr = self._mmr(limit, diversity, fetch_k, expand)
+        mmr = self._mmr(limit, diversity, fetch_k, expand, boost)
         with tracer.stage("embed_query", self._device):
             q = self._get_embedding(query)
         with self._graph_lock:
@@ -674,16 +683,16 @@ class MemorySystem(ConsolidationMixin):
             return [n for n in (self.buffer.get_node(i) for i in ids) if n is not None]
 
     def search_memories_batch(self, queries: List[str], limit: int = 5, where=None, diversity=None,
-                              fetch_k=None, expand=None) -> List[List[Node]]:
+                              fetch_k=None, expand=None, boost=None) -> List[List[Node]]:
         """Batched ``search_memories`` (reference :1460-1472 per query): one
         embedding call (a device tensor when the encoder is on-device), one
         store search -- the fused MFMA candidate scan plus an fp32 re-rank
         over the tenant's HBM rows -- and one row -> Node mapping. ``where``,
-        ``diversity``, ``fetch_k``, ``expand``: one setting for the whole
-        batch (see :meth:`search_memories`)."""
+        ``diversity``, ``fetch_k``, ``expand``, ``boost``: one setting for the
+        whole batch (see :meth:`search_memories`)."""
         if where is not None:
             where = self._where(where)
-        mmr = self._mmr(limit, diversity, fetch_k, expand)
+        mmr = self._mmr(limit, diversity, fetch_k, expand, boost)
         t0 = time.perf_counter()
         out = self._search_finish(self._search_submit(queries, limit, where, mmr))
         self._count_search(len(out), (time.perf_counter() - t0) * 1e3)
@@ -696,17 +705,18 @@ class MemorySystem(ConsolidationMixin):
         m["search_ms"] = m.get("search_ms", 0.0) + ms
 
     def search_memories_stream(self, batches: Iterable[List[str]], limit: int = 5, where=None, diversity=None,
-                               fetch_k=None, expand=None):
+                               fetch_k=None, expand=None, boost=None):
         """Pipelined ``search_memories_batch`` for serving loops: batches i+1 ..
         i+STREAM_DEPTH are tokenised and their embed + scan enqueued on the
         device BEFORE the host waits for batch i and maps its rows to Nodes,
         so host work (tokenizer, result mapping) hides under device work.
         Yields one result list per input batch, in order; results equal
         ``search_memories_batch``. ``where``, ``diversity``, ``fetch_k``,
-        ``expand``: one setting for all batches."""
+        ``expand``, ``boost``: one setting for all batches (a boost's ``now``
+        is read once, for the whole stream)."""
         if where is not None:
             where = self._where(where)
-        mmr = self._mmr(limit, diversity, fetch_k, expand)
+        mmr = self._mmr(limit, diversity, fetch_k, expand, boost)
         pending = collections.deque()
         for qs in batches:
             pending.append(self._search_submit(qs, limit, where, mmr))
@@ -837,7 +847,8 @@ class MemorySystem(ConsolidationMixin):
                 "ann_upserts": g.ann_upserts, "ann_rebuilds": g.ann_rebuilds,
                 "filtered_searches": g.filtered_searches, "filter_plans_built": g.filter_plans_built,
                 "filtered_sparse": g.filtered_sparse, "filtered_ann": g.filtered_ann,
-                "mmr_searches": g.mmr_searches, "expanded_searches": g.expanded_searches, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
+                "mmr_searches": g.mmr_searches, "expanded_searches": g.expanded_searches,
+                "boosted_searches": g.boosted_searches, "boost_columns_built": g.boost_columns_built, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
                 "avg_search_batch_ms": round(sms / m["search_batches"], 3) if m.get("search_batches") else 0.0}
 
     def _graph_bytes(self) -> int:

@@ -279,15 +279,20 @@ class HBMStore:
         raise NotImplementedError(
             f"an expanded search (expand=) needs the tenant's graph attached to the store; {user_id!r} has none")
 
+    def _boost_needs_graph(self, user_id: str):
+        raise NotImplementedError(
+            f"a boosted search (boost=) needs the tenant's graph attached to the store; {user_id!r} has none")
+
     def search_nodes(self, query_emb, user_id: str = "default", limit: int = 5, where=None, diversity=None,
-                     fetch_k=None, expand=None) -> List[str]:
+                     fetch_k=None, expand=None, boost=None) -> List[str]:
         """``where`` (a MemoryFilter or a dict of its fields): only the
         tenant's memories passing it are searched (core/filters.py).
         ``diversity`` / ``fetch_k``: the results are picked from the
         ``fetch_k`` nearest by maximal marginal relevance, in pick order
         (TenantGraph.store_search). ``expand``: the links of the nearest are
         followed and the best of everything reached come back
-        (core/expand.py)."""
+        (core/expand.py). ``boost``: the best by closeness plus a prior from
+        salience, use and recency (core/boost.py)."""
         if query_emb is None or len(query_emb) == 0:
             return []
         g = self._graphs.get(user_id)
@@ -298,14 +303,16 @@ class HBMStore:
             self._mmr_needs_graph(user_id)
         if expand is not None and g is None:
             self._expand_needs_graph(user_id)
+        if boost is not None and g is None:
+            self._boost_needs_graph(user_id)
         if g is not None:
             q = query_emb if torch.is_tensor(query_emb) else torch.from_numpy(
                 np.asarray(query_emb, dtype=np.float32))
             with g.lock:  # the tenant's graph lock: a consolidation may be writing
                 if g.dim is None or q.shape[-1] != g.dim:
                     return []
-                if mmr or expand is not None:
-                    return g.search_ids(q, int(limit), self.metric, where, diversity, fetch_k, expand)[0]
+                if mmr or expand is not None or boost is not None:
+                    return g.search_ids(q, int(limit), self.metric, where, diversity, fetch_k, expand, boost)[0]
                 return g.search_ids(q, int(limit), self.metric, where)[0]
         with self._lock:  # writers (add/delete/replace) mutate the arena in place
             a = self._arena(user_id)
@@ -314,11 +321,11 @@ class HBMStore:
             return a.search(query_emb, int(limit), self.metric)[0]
 
     def search_nodes_batch(self, query_embs, user_id: str = "default", limit: int = 5,
-                           where=None, diversity=None, fetch_k=None, expand=None) -> List[List[str]]:
+                           where=None, diversity=None, fetch_k=None, expand=None, boost=None) -> List[List[str]]:
         """Batched variant (one kernel launch for all queries). ``query_embs``
         may be a device tensor (kept on the device end to end). ``where``,
-        ``diversity``, ``fetch_k``, ``expand``: one setting for the whole
-        batch (see :meth:`search_nodes`)."""
+        ``diversity``, ``fetch_k``, ``expand``, ``boost``: one setting for the
+        whole batch (see :meth:`search_nodes`)."""
         g = self._graphs.get(user_id)
         if where is not None and g is None:
             self._filter_needs_graph(user_id)
@@ -327,6 +334,8 @@ class HBMStore:
             self._mmr_needs_graph(user_id)
         if expand is not None and g is None:
             self._expand_needs_graph(user_id)
+        if boost is not None and g is None:
+            self._boost_needs_graph(user_id)
         if g is not None:
             Q = query_embs if torch.is_tensor(query_embs) else torch.as_tensor(
                 np.asarray(query_embs, dtype=np.float32))
@@ -335,8 +344,8 @@ class HBMStore:
             with g.lock:
                 if g.dim is None or Q.shape[-1] != g.dim:
                     return [[] for _ in range(len(Q))]
-                if mmr or expand is not None:
-                    return g.search_ids(Q, int(limit), self.metric, where, diversity, fetch_k, expand)
+                if mmr or expand is not None or boost is not None:
+                    return g.search_ids(Q, int(limit), self.metric, where, diversity, fetch_k, expand, boost)
                 return g.search_ids(Q, int(limit), self.metric, where)
         with self._lock:
             a = self._arena(user_id)
@@ -345,11 +354,12 @@ class HBMStore:
             return a.search(query_embs, int(limit), self.metric)
 
     def search_nodes_multi(self, query_embs, user_ids: Sequence[str], limit: int = 5, where=None, diversity=None,
-                           fetch_k=None, expand=None) -> List[List[str]]:
+                           fetch_k=None, expand=None, boost=None) -> List[List[str]]:
         """Multi-tenant batch: query i searches tenant ``user_ids[i]`` only, all
         in one kernel launch (serving many users per GPU, BASELINE config 3).
-        Filters, diverse selection and graph expansion are not supported here
-        (``where``, ``diversity``, ``fetch_k`` and ``expand`` raise)."""
+        Filters, diverse selection, graph expansion and boosts are not
+        supported here (``where``, ``diversity``, ``fetch_k``, ``expand`` and
+        ``boost`` raise)."""
         from ..index.arena import multi_arena_search
         if where is not None:
             raise NotImplementedError("search_nodes_multi does not take a filter; search each tenant with where=")
@@ -359,6 +369,8 @@ class HBMStore:
         if expand is not None:
             raise NotImplementedError("search_nodes_multi does not expand along links; search each tenant with "
                                       "expand=")
+        if boost is not None:
+            raise NotImplementedError("search_nodes_multi does not boost; search each tenant with boost=")
         if len(user_ids) == 0:
             return []
         with self._lock:

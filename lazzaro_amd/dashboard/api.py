@@ -107,14 +107,19 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
                  accessed_since: Optional[float] = None, min_access_count: Optional[int] = None,
                  super_nodes: Optional[bool] = None, exclude_ids: Optional[str] = None,
                  diversity: Optional[float] = None, fetch_k: Optional[int] = None,
-                 hops: Optional[int] = None, fanout: Optional[int] = None, graph_weight: Optional[float] = None):
+                 hops: Optional[int] = None, fanout: Optional[int] = None, graph_weight: Optional[float] = None,
+                 boost: Optional[float] = None, boost_recency_scale: Optional[float] = None):
     """``MemoryFilter`` fields as optional query parameters (the set-valued
     ones comma separated); none given: the unfiltered search. ``diversity``
     (0 .. 1) and ``fetch_k``: results picked for diversity from the
     ``fetch_k`` nearest (``MemorySystem.search_memories``). ``hops``,
     ``fanout``, ``graph_weight``: any of them given makes it an associative
     search along the memories' links (``expand=``, core/expand.py; the others
-    keep their defaults)."""
+    keep their defaults). ``boost`` (a weight ``w``): the results are ranked
+    by closeness plus ``w`` times each memory's importance -- salience 0.5 w,
+    use 0.3 w, recency 0.2 w (``boost=``, core/boost.py);
+    ``boost_recency_scale``: the recency term's scale in seconds (default one
+    day; given alone it changes nothing)."""
     if not _ms:
         return []
     where = {k: v for k, v in (("types", _csv(types)), ("shard_keys", _csv(shard_keys)),
@@ -128,6 +133,12 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
     expand = {k: v for k, v in (("hops", hops), ("fanout", fanout), ("graph_weight", graph_weight)) if v is not None}
     if expand:
         kw.update(expand=expand)
+    if boost is not None:
+        from ..core.boost import MemoryBoost
+        b = MemoryBoost.coerce(float(boost)).to_dict()
+        if boost_recency_scale is not None:
+            b["recency_scale"] = boost_recency_scale
+        kw.update(boost=b)
     hits = _ms.search_memories(q, limit=limit, **kw)
     return [{"id": n.id, "content": n.content, "salience": n.salience, "shard": n.shard_key} for n in hits]
 

@@ -185,6 +185,7 @@ FILTER_SPARSE_MAX_ROWS = 1 << 19
 # while its time grows with the scale and recall@10 slipped below 0.998 at scale 32
 FILTER_ANN_MAX_SCALE = 8
 FILTER_PLAN_CACHE = 8  # plans kept per graph (LRU); a plan holds 4 n bytes of bias + 4 bytes per listed row
+BOOST_COLUMN_CACHE = 2  # boosted bias columns kept per graph (LRU), 4 n bytes each
 
 
 def _str_column(items=None):
@@ -2456,7 +2457,7 @@ class TenantGraph:
         return b
 
     def store_search(self, Q: torch.Tensor, k: int, metric: str = "l2", node_rows: bool = False, where=None,
-                     diversity: Optional[float] = None, fetch_k: Optional[int] = None, expand=None):
+                     diversity: Optional[float] = None, fetch_k: Optional[int] = None, expand=None, boost=None):
         """The store's vector search over this tenant (reference
         ``LanceDBStore.search_nodes``: flat scan, L2 unless told otherwise,
         vector_store.py:132-140). fp32 scores -- -|q-x|^2 for L2, cosine, or
@@ -2474,11 +2475,29 @@ class TenantGraph:
         the links of the nearest rows are walked and the ``k`` best of
         everything reached come back with blended scores
         (:meth:`store_search_expand`, which also returns ``via``; seeds and
-        targets are graph nodes, so ``node_rows`` changes nothing then)."""
+        targets are graph nodes, so ``node_rows`` changes nothing then).
+        ``boost`` (a number, a dict or a ``core.boost.MemoryBoost``): the
+        ``k`` rows with the largest ``score + prior`` among the graph nodes in
+        the store, the prior built from salience, use and recency
+        (:meth:`boost_bias`); the scores returned include it. With
+        ``diversity`` / ``expand`` it decides their pool / seeds only."""
+        if boost is not None:
+            from ..core.boost import MemoryBoost
+            boost = MemoryBoost.coerce(boost).at()  # (``now`` is read once, here)
         if diversity is not None or fetch_k is not None:
-            return self._store_search_mmr(Q, k, metric, node_rows, where, diversity, fetch_k, expand)
+            return self._store_search_mmr(Q, k, metric, node_rows, where, diversity, fetch_k, expand, boost)
         if expand is not None:
-            return self.store_search_expand(Q, k, metric, where, expand)[:2]
+            return self.store_search_expand(Q, k, metric, where, expand, boost)[:2]
+        if boost is not None:
+            with self.on_stream():
+                self.boosted_searches += 1
+                if where is not None:
+                    return self._store_search_where(Q, k, metric, where, boost)
+                if self.n == 0 or self.dim is None:
+                    return self._store_search(Q, k, metric)
+                # a plan-like bias holder: the flat routes of _store_search, never the IVF-PQ index
+                # (its candidate stage cannot see the prior)
+                return self._store_search(Q, k, metric, False, self._boost_plan(boost, metric))
         if where is not None:
             with self.on_stream():
                 return self._store_search_where(Q, k, metric, where)
@@ -2493,12 +2512,13 @@ class TenantGraph:
 
     mmr_searches = 0
 
-    def _store_search_mmr(self, Q, k, metric, node_rows, where, diversity, fetch_k, expand=None):
+    def _store_search_mmr(self, Q, k, metric, node_rows, where, diversity, fetch_k, expand=None, boost=None):
         """:meth:`store_search` with ``diversity``: the pool is the plain
         search at ``k = fetch_k`` (default ``max(16, 2 k)``, at most
         MAX_FETCH_K = 64) by whatever route that takes, ``node_rows`` and
         ``where`` passed through (with ``expand``, the expanded search at
-        ``k = fetch_k`` and its blended scores); rows it marked -1 are not
+        ``k = fetch_k`` and its blended scores; with ``boost``, the boosted
+        search at ``k = fetch_k`` and its boosted scores); rows it marked -1 are not
         candidates. The ``k`` picks are greedy maximal marginal relevance
         over the pool's fp32 rows (ops.mmr_ops.mmr_select: cosine relevance
         and cosine redundancy whatever the metric, ties to the lower row),
@@ -2507,7 +2527,7 @@ class TenantGraph:
         from ..ops.mmr_ops import mmr_select, pool_size
         k = int(k)
         F = pool_size(k, diversity, fetch_k)
-        s, r = self.store_search(Q, F, metric, node_rows, where, expand=expand)
+        s, r = self.store_search(Q, F, metric, node_rows, where, expand=expand, boost=boost)
         self.mmr_searches += 1
         with self.on_stream():
             Qf = Q.to(self.device, torch.float32)
@@ -2523,11 +2543,12 @@ class TenantGraph:
 
     expanded_searches = 0
 
-    def store_search_expand(self, Q, k, metric: str = "l2", where=None, expand=1):
+    def store_search_expand(self, Q, k, metric: str = "l2", where=None, expand=1, boost=None):
         """:meth:`store_search` with ``expand``, returning (scores [M, k], rows
         [M, k], via [M, k]). The seeds are the plain search at ``k = seed_k``
-        with ``node_rows=True`` by whatever route that takes, ``where`` passed
-        through; the visible-arc CSR (:meth:`csr`) is walked from them
+        with ``node_rows=True`` by whatever route that takes, ``where`` and
+        ``boost`` passed through (a boost picks the seeds and nothing else:
+        the blend below stays cosine); the visible-arc CSR (:meth:`csr`) is walked from them
         (ops.expand_ops.expand_select holds the contract: ``hops`` Jacobi
         hops, the first ``fanout`` arcs of weight ``>= min_weight`` per
         source, max-product activation). Targets are graph nodes whose search
@@ -2544,7 +2565,7 @@ class TenantGraph:
         k = int(k)
         sp = GraphExpand.coerce(expand)
         pool_bound(sp, k)
-        _, seeds = self.store_search(Q, sp.seed_k, metric, True, where)
+        _, seeds = self.store_search(Q, sp.seed_k, metric, True, where, boost=boost)
         self.expanded_searches += 1
         dev = self.device
         Qf = Q.to(dev, torch.float32)
@@ -2566,6 +2587,70 @@ class TenantGraph:
             rows, scores, via, _ = expand_select(self.emb32[:n], Qf, seeds, csr, self.e["w"], self.kind, self.sup,
                                                  bias, sp, k)
         return scores, rows, via
+
+    # ---- boosted search
+    _boost_cols = None  # OrderedDict: column key -> FilterPlan holding the boosted column (LRU, BOOST_COLUMN_CACHE)
+    boosted_searches = boost_columns_built = 0
+
+    def boost_bias(self, boost, metric: str = "l2", where=None, now: Optional[float] = None) -> torch.Tensor:
+        """The bias column of a boosted search, fp32 [n] (ops/boost_ops.py
+        holds the contract): ``base[r] + prior(r)`` where row ``r`` is a graph
+        node, -inf elsewhere; ``base`` is :meth:`store_bias`, or under
+        ``where`` the filter plan's bias. ``now``: the clock reading for
+        settings that carry none (default ``time.time()``)."""
+        from ..core.boost import MemoryBoost
+        from ..core.filters import MemoryFilter
+        b = MemoryBoost.coerce(boost).at(now)
+        if self.n == 0 or self.dim is None:
+            return torch.empty(0, dtype=torch.float32, device=self.device)
+        with self.on_stream():
+            if where is None:
+                return self._boost_plan(b, metric).bias
+            flt = MemoryFilter.coerce(where)
+            return self._boost_plan(b, metric, flt, self._filter_plan(flt, metric == "l2")).bias
+
+    def _boost_plan(self, boost, metric: str, flt=None, plan=None):
+        """The boosted column of ``boost`` (``now`` set) as a plan the search
+        routes take: the filter plan's rows and count with the column as its
+        bias, or -- unfiltered -- the column alone. Cached (LRU of
+        BOOST_COLUMN_CACHE columns, 4 n bytes each) under the settings, the
+        metric's scale, the filter and the counters :meth:`_filter_plan` keys
+        on, so a column is never served after a write it could depend on (a
+        retrieval touch bumps ``version``). One launch, no host
+        synchronisation."""
+        from collections import OrderedDict
+
+        from ..ops.boost_ops import boost_bias, metric_scale
+        if self._boost_cols is None:
+            self._boost_cols = OrderedDict()
+        cache = self._boost_cols
+        l2 = metric == "l2"
+        n = self.n
+        tw = None
+        if boost.type_weights:
+            self._type_codes()  # (may not change the counters; a rewritten type bumped _meta_gen already)
+            tw = [0.0] * 256
+            for name, w in boost.type_weights.items():
+                code = self.type_code.get(name)
+                if code is not None:  # a type the tenant never saw adds nothing
+                    tw[code] = w
+        key = (boost.key(), l2, None if flt is None else flt.key(), self.version, self._store_version, self.row_epoch,
+               n, self._meta_gen)
+        hit = cache.get(key)
+        if hit is not None:
+            cache.move_to_end(key)
+            return hit
+        base = self.store_bias("l2" if l2 else "ip") if plan is None else plan.bias
+        t = self.last if boost.clock == "accessed" else self.ts
+        col = boost_bias(base, self.sal, self.acc, t, self.kind, n, boost.salience, boost.frequency, boost.recency,
+                         boost.recency_scale, boost.now, metric_scale(metric),
+                         self._tcode if tw is not None else None, tw)
+        out = FilterPlan(col, None if plan is None else plan.rows, n if plan is None else plan.count)
+        self.boost_columns_built += 1
+        cache[key] = out
+        while len(cache) > BOOST_COLUMN_CACHE:
+            cache.popitem(last=False)
+        return out
 
     # ---- filtered search: state (class defaults; the containers are made on first use)
     _meta_gen = 0  # bumps on a scalar column write that bumps no other counter (set_scalar)
@@ -2683,7 +2768,7 @@ class TenantGraph:
             cache.popitem(last=False)
         return plan
 
-    def _store_search_where(self, Q, k, metric, where):
+    def _store_search_where(self, Q, k, metric, where, boost=None):
         """:meth:`store_search` restricted to the rows passing ``where``.
         Routes: no passing row -> all -1, no scan; on the GPU (L2, IP,
         cosine over unit rows), while rows x query tiles stays within
@@ -2701,7 +2786,9 @@ class TenantGraph:
         the plan until the index's ``order_gen`` moves), ``filtered_nprobe``
         lists probed, the exact PQ top-R among passing rows re-ranked in fp32
         with the plan's bias as row mask (every returned row passes whatever
-        the lists held)."""
+        the lists held). ``boost``: the plan's bias column is replaced by the
+        boosted one (:meth:`_boost_plan`; the row list is the plan's own), and
+        the index route is never taken."""
         from ..core.filters import MemoryFilter
         flt = MemoryFilter.coerce(where)
         n = self.n
@@ -2716,6 +2803,8 @@ class TenantGraph:
         plan = self._filter_plan(flt, metric == "l2")
         if plan.count == 0:
             return (torch.full((M, k), NEG_INF, device=dev), torch.full((M, k), -1, dtype=torch.long, device=dev))
+        if boost is not None:
+            plan = self._boost_plan(boost, metric, flt, plan)
         # (the indexed scan reads every listed row once per tile of 8 queries)
         if self.on_gpu and plan.count * -(-M // 8) <= FILTER_SPARSE_MAX_ROWS and k <= CAND_SLOTS \
                 and (metric != "cosine" or self.unit_rows()):
@@ -2728,7 +2817,7 @@ class TenantGraph:
                                   2.0 if metric == "l2" else 1.0)
             return self._rerank_store(Qf, cand, k, metric, plan.bias)
         cfg = self.ann_cfg
-        if cfg is not None and cfg.get("filtered") and n >= cfg["min_rows"] and self.unit_rows() \
+        if cfg is not None and cfg.get("filtered") and boost is None and n >= cfg["min_rows"] and self.unit_rows() \
                 and n <= FILTER_ANN_MAX_SCALE * plan.count:
             self.filtered_ann += 1
             if metric == "cosine":
@@ -2982,11 +3071,11 @@ class TenantGraph:
         return self._pad_k(torch.gather(s, 1, o), torch.gather(cand, 1, o), k)
 
     def search_ids(self, Q, k: int, metric: str = "l2", where=None, diversity=None, fetch_k=None,
-                   expand=None) -> List[List[str]]:
-        if diversity is not None or fetch_k is not None or expand is not None:
+                   expand=None, boost=None) -> List[List[str]]:
+        if diversity is not None or fetch_k is not None or expand is not None or boost is not None:
             # (node rows only: a row the caller would drop must not take a pick)
             _, r = self.store_search(Q, k, metric, node_rows=True, where=where, diversity=diversity, fetch_k=fetch_k,
-                                     expand=expand)
+                                     expand=expand, boost=boost)
         else:
             _, r = self.store_search(Q, k, metric, where=where)
         ids = self.ids
@@ -3376,6 +3465,7 @@ class TenantGraph:
         self._nodes_marked = False
         self._tcode, self._tcode_n, self._tcode_dirty = None, 0, None  # rebuilt by the next type filter
         self._filter_plans = None
+        self._boost_cols = None
         if shrink:
             cap = max(self._init_cap, math.ceil(1.1 * m))
             if cap != self.cap:
