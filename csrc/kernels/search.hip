@@ -21,6 +21,7 @@
 //     registers (threshold compare fast path, insertion rarely taken).
 //   * Two-stage: per-(query, chunk) partial top-K, then topk_merge.
 #include "lzk_tile.h"
+#include "lzk_i8score.h"
 
 #include <cstdlib>
 
@@ -61,6 +62,52 @@ struct TopK {
     }
   }
 };
+
+// The 4 lane lists a query has in a 128x128 tile's workgroup (2 row-waves x 2
+// half-waves, each sorted, rows offered in increasing order) merged by
+// (score desc, row asc) into the (query, chunk) partial list. Every thread of
+// the block calls it after the K loop's last barrier (smem is reused).
+template <int K>
+__device__ __forceinline__ void merge_lane_lists(u16* smem, const TopK<K> (&top)[2], int q0, int nq, int n_chunks,
+                                                 int chunk, float* __restrict__ out_s, int* __restrict__ out_i) {
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int wrow = wave >> 1, wcol = wave & 1;
+  const int h = lane >> 5, l32 = lane & 31;
+  float* ms = reinterpret_cast<float*>(smem);
+  int* mi = reinterpret_cast<int*>(smem) + BN * 4 * K;
+#pragma unroll
+  for (int cb = 0; cb < 2; ++cb) {
+    int ql = wcol * 64 + cb * 32 + l32;
+    int li = wrow * 2 + h;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      ms[(ql * 4 + li) * K + j] = top[cb].s[j];
+      mi[(ql * 4 + li) * K + j] = top[cb].i[j];
+    }
+  }
+  __syncthreads();
+  if (tid < BN) {
+    const int ql = tid;
+    const int q = q0 + ql;
+    if (q < nq) {
+      int p0 = 0, p1 = 0, p2 = 0, p3 = 0;
+      const float* bs = ms + ql * 4 * K;
+      const int* bi = mi + ql * 4 * K;
+      long obase = ((long)q * n_chunks + chunk) * K;
+      for (int j = 0; j < K; ++j) {
+        float bsv = LZK_NEG_INF; int biv = -1; int w = -1;
+        if (p0 < K) { float s = bs[0 * K + p0]; int i = bi[0 * K + p0]; if (w < 0 || better(s, i, bsv, biv)) { bsv = s; biv = i; w = 0; } }
+        if (p1 < K) { float s = bs[1 * K + p1]; int i = bi[1 * K + p1]; if (w < 0 || better(s, i, bsv, biv)) { bsv = s; biv = i; w = 1; } }
+        if (p2 < K) { float s = bs[2 * K + p2]; int i = bi[2 * K + p2]; if (w < 0 || better(s, i, bsv, biv)) { bsv = s; biv = i; w = 2; } }
+        if (p3 < K) { float s = bs[3 * K + p3]; int i = bi[3 * K + p3]; if (w < 0 || better(s, i, bsv, biv)) { bsv = s; biv = i; w = 3; } }
+        p0 += (w == 0); p1 += (w == 1); p2 += (w == 2); p3 += (w == 3);
+        out_s[obase + j] = bsv;
+        out_i[obase + j] = (bsv == LZK_NEG_INF) ? -1 : biv;
+      }
+    }
+  }
+}
 
 template <int K, bool HAS_BIAS, bool HAS_LABEL, bool GLDS>
 __global__ __launch_bounds__(NT, 2) void flat_topk_kernel(
@@ -309,40 +356,185 @@ __global__ __launch_bounds__(NT, 2) void flat_topk_kernel(
     ks = nks; rt = nrt;
   }
 
-  // ---- merge the 4 per-query lane lists (2 row-waves x 2 half-waves) ----
-  float* ms = reinterpret_cast<float*>(smem);
-  int* mi = reinterpret_cast<int*>(smem) + BN * 4 * K;
+  merge_lane_lists<K>(smem, top, q0, nq, n_chunks, chunk, out_s, out_i);
+}
+
+// The int8 store search's threshold sample: flat_topk_kernel's tile, LDS
+// image, LDS-DMA staging, barrier scheme and lane-local top-K over the rows
+// 0, S, 2S, ... of the int8 copy, read in place (row stride S * ldx bytes;
+// row scales and bias strided by S). A 128-byte LDS row holds 128 int8 K
+// values instead of 64 bf16, so v_mfma_i32_32x32x32_i8 takes the same two
+// 16-byte chunks per lane as the bf16 32x32x16 form: half the K steps, half
+// the bytes. The integer sums are exact, and the score is the scan's
+// (i8_prod / i8_score with al = alpha * qs[q]): a sample row scores here
+// bit for bit what flat_cand_persistent_kernel<..., MmaI8> gives it. `ns` =
+// sample rows; partial lists carry the REAL row r * S.
+template <int K, bool HAS_BIAS>
+__global__ __launch_bounds__(NT, 2) void sample_topk_i8_kernel(
+    const int8_t* __restrict__ X, long ldx, int ns, int S,
+    const int8_t* __restrict__ Qm, long ldq, int nq,
+    const float* __restrict__ rscale, const float* __restrict__ qscale, const float* __restrict__ bias,
+    float alpha, int D, int rows_per_chunk, int n_chunks, int n_qblocks,
+    float* __restrict__ out_s, int* __restrict__ out_i) {
+  typedef int i32x4 __attribute__((ext_vector_type(4)));
+  typedef int i32x16 __attribute__((ext_vector_type(16)));
+  constexpr int BKB = 2 * BK;  // K values (= bytes) per stage: the same 128-byte LDS rows
+  extern __shared__ __attribute__((aligned(16))) u16 smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int wrow = wave >> 1, wcol = wave & 1;
+  const int h = lane >> 5, l32 = lane & 31;
+
+  const int logical = xcd_remap(blockIdx.x, gridDim.x);
+  const int chunk = logical / n_qblocks;
+  const int qb = logical % n_qblocks;
+  if (chunk >= n_chunks) return;
+  const int q0 = qb * BN;
+  const int row_lo = chunk * rows_per_chunk;
+  const int row_hi = min(ns, row_lo + rows_per_chunk);
+  const int ntiles = (row_hi > row_lo) ? (row_hi - row_lo + BM - 1) / BM : 0;
+  const int KSTEPS = D / BKB;
+  const int T = ntiles * KSTEPS;
+
+  // al = alpha * query scale for the lane's two query columns
+  float al[2];
 #pragma unroll
-  for (int cb = 0; cb < 2; ++cb) {
-    int ql = wcol * 64 + cb * 32 + l32;
-    int li = wrow * 2 + h;
+  for (int cb = 0; cb < 2; ++cb) al[cb] = alpha * qscale[min(q0 + wcol * 64 + cb * 32 + l32, nq - 1)];
+
+  TopK<K> top[2];
+  top[0].init(); top[1].init();
+
+  // LDS-DMA staging: per-lane pre-swizzled sources, wave-uniform 1 KiB pieces
+  const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+  const int8_t* gx[4];
+  const int8_t* gq[4];
+  int gpiece[4];
 #pragma unroll
-    for (int j = 0; j < K; ++j) {
-      ms[(ql * 4 + li) * K + j] = top[cb].s[j];
-      mi[(ql * 4 + li) * K + j] = top[cb].i[j];
-    }
+  for (int i = 0; i < 4; ++i) {
+    const int c = wave_u * 4 + i;
+    const int row = 8 * c + (lane >> 3);
+    const int kc = (lane & 7) ^ ((row >> 1) & 7);
+    gq[i] = Qm + (long)min(q0 + row, nq - 1) * ldq + kc * 16;
+    gx[i] = X;
+    gpiece[i] = c * 512;
   }
-  __syncthreads();
-  if (tid < BN) {
-    const int ql = tid;
-    const int q = q0 + ql;
-    if (q < nq) {
-      int p0 = 0, p1 = 0, p2 = 0, p3 = 0;
-      const float* bs = ms + ql * 4 * K;
-      const int* bi = mi + ql * 4 * K;
-      long obase = ((long)q * n_chunks + chunk) * K;
-      for (int j = 0; j < K; ++j) {
-        float bsv = LZK_NEG_INF; int biv = -1; int w = -1;
-        if (p0 < K) { float s = bs[0 * K + p0]; int i = bi[0 * K + p0]; if (w < 0 || better(s, i, bsv, biv)) { bsv = s; biv = i; w = 0; } }
-        if (p1 < K) { float s = bs[1 * K + p1]; int i = bi[1 * K + p1]; if (w < 0 || better(s, i, bsv, biv)) { bsv = s; biv = i; w = 1; } }
-        if (p2 < K) { float s = bs[2 * K + p2]; int i = bi[2 * K + p2]; if (w < 0 || better(s, i, bsv, biv)) { bsv = s; biv = i; w = 2; } }
-        if (p3 < K) { float s = bs[3 * K + p3]; int i = bi[3 * K + p3]; if (w < 0 || better(s, i, bsv, biv)) { bsv = s; biv = i; w = 3; } }
-        p0 += (w == 0); p1 += (w == 1); p2 += (w == 2); p3 += (w == 3);
-        out_s[obase + j] = bsv;
-        out_i[obase + j] = (bsv == LZK_NEG_INF) ? -1 : biv;
+  auto set_gx = [&](int rt_) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = 8 * (wave_u * 4 + i) + (lane >> 3);
+      const int kc = (lane & 7) ^ ((row >> 1) & 7);
+      gx[i] = X + (long)min(row_lo + rt_ * BM + row, ns - 1) * S * ldx + kc * 16;
+    }
+  };
+  // per-row epilogue operands (bias, row scale) of a row tile: a small
+  // double-buffered LDS area indexed by row-tile parity
+  float* ebias = reinterpret_cast<float*>(smem + 4 * TILE_ELEMS);
+  float* ers = ebias + 2 * BM;
+  auto gissue = [&](int buf, int ks_, int rt_) {
+    u16* xs = smem + buf * 2 * TILE_ELEMS;
+    u16* qs = xs + TILE_ELEMS;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      __builtin_amdgcn_global_load_lds((lzk::gbl_void_t*)(gx[i] + ks_ * BKB), (lzk::lds_void_t*)(xs + gpiece[i]), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((lzk::gbl_void_t*)(gq[i] + ks_ * BKB), (lzk::lds_void_t*)(qs + gpiece[i]), 16, 0, 0);
+    }
+    if (ks_ == 0 && wave_u == 0) {
+#pragma unroll
+      for (int h2 = 0; h2 < 2; ++h2) {
+        const long r = (long)min(row_lo + rt_ * BM + h2 * 64 + lane, ns - 1) * S;
+        __builtin_amdgcn_global_load_lds((lzk::gbl_void_t*)(rscale + r), (lzk::lds_void_t*)(ers + (rt_ & 1) * BM + h2 * 64), 4, 0, 0);
+        if (HAS_BIAS)
+          __builtin_amdgcn_global_load_lds((lzk::gbl_void_t*)(bias + r), (lzk::lds_void_t*)(ebias + (rt_ & 1) * BM + h2 * 64), 4, 0, 0);
       }
     }
+  };
+
+  i32x16 acc[2][2];
+
+  if (T > 0) {
+    set_gx(0);
+    gissue(0, 0, 0);
+    lzk::vm_drain();
   }
+  __syncthreads();
+
+  int rt = 0, ks = 0;
+  for (int t = 0; t < T; ++t) {
+    const bool has_next = (t + 1 < T);
+    const int nks = (ks + 1 == KSTEPS) ? 0 : ks + 1;
+    const int nrt = (ks + 1 == KSTEPS) ? rt + 1 : rt;
+    if (has_next) {
+      if (nks == 0) set_gx(nrt);
+      gissue((t + 1) & 1, nks, nrt);
+    }
+    if (ks == 0) {
+#pragma unroll
+      for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) acc[a][b][e] = 0;
+    }
+    // ---- MFMA over this K-step ----
+    __builtin_amdgcn_s_setprio(1);
+    {
+      const u16* xs = smem + (t & 1) * 2 * TILE_ELEMS;
+      const u16* qs = xs + TILE_ELEMS;
+#pragma unroll
+      for (int s = 0; s < BKB / 32; ++s) {
+        i32x4 af[2], bfr[2];
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb) {
+          int r = wrow * 64 + rb * 32 + l32;
+          af[rb] = *reinterpret_cast<const i32x4*>(xs + swz_off(r, 2 * s + h));
+        }
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+          int r = wcol * 64 + cb * 32 + l32;
+          bfr[cb] = *reinterpret_cast<const i32x4*>(qs + swz_off(r, 2 * s + h));
+        }
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+          for (int cb = 0; cb < 2; ++cb)
+            acc[rb][cb] = __builtin_amdgcn_mfma_i32_32x32x32_i8(af[rb], bfr[cb], acc[rb][cb], 0, 0, 0);
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);
+    // ---- fused top-k epilogue at the end of a row tile ----
+    if (ks == KSTEPS - 1) {
+      const int lrow0 = wrow * 64 + 4 * h;
+      const int tile0 = row_lo + rt * BM + lrow0;
+      const float* eb = ebias + (rt & 1) * BM + lrow0;
+      const float* er = ers + (rt & 1) * BM + lrow0;
+      const bool full_tile = row_lo + (rt + 1) * BM <= row_hi;  // wave-uniform
+      auto score = [&](int rb, int cb, int e) -> float {
+        const int lr = rb * 32 + 8 * (e >> 2) + (e & 3);
+        const float x = i8_score(al[cb], i8_prod(acc[rb][cb][e], er[lr]), HAS_BIAS ? eb[lr] : 0.f);
+        const bool ok = full_tile || tile0 + lr < row_hi;
+        return ok ? x : LZK_NEG_INF;
+      };
+#pragma unroll
+      for (int rb = 0; rb < 2; ++rb) {
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+          float m = LZK_NEG_INF;
+#pragma unroll
+          for (int e = 0; e < 16; ++e) m = fmaxf(m, score(rb, cb, e));
+          if (m > top[cb].s[K - 1]) {
+#pragma unroll
+            for (int e = 0; e < 16; ++e)
+              top[cb].push(score(rb, cb, e), (tile0 + rb * 32 + (e & 3) + 8 * (e >> 2)) * S);
+          }
+        }
+      }
+    }
+    lzk::vm_drain();
+    __syncthreads();
+    ks = nks; rt = nrt;
+  }
+  merge_lane_lists<K>(smem, top, q0, nq, n_chunks, chunk, out_s, out_i);
 }
 
 // Merge per-(query, chunk) partial lists into the final top-k. One wave per
@@ -565,6 +757,47 @@ LZK_EXPORT int lzk_flat_topk_partial_masked(const void* X, long ldx, int nrows, 
                                             const int* q_active, void* stream) {
   return flat_partial(X, ldx, nrows, Qm, ldq, nq, bias, row_label, q_label, alpha, D, kslot, n_chunks, ps, pi,
                       stream, q_active);
+}
+
+// Threshold sample of the int8 store search: per-(query, chunk) partial
+// top-kslot lists over the rows 0, S, 2S, ... (< nrows) of X8 [nrows, D] int8,
+// scored like the int8 scan (rscale [nrows], qscale [nq], optional bias
+// [nrows], alpha). ps/pi are [nq, n_chunks, kslot] with n_chunks =
+// lzk_flat_topk_chunks(ceil(nrows / S), nq, ...); pi holds real rows.
+// lzk_topk_merge turns them into the per-query top-kslot.
+LZK_EXPORT int lzk_sample_topk_i8(const void* X8, long ldx, int nrows, int S, const void* Q8, long ldq, int nq,
+                                  const float* rscale, const float* qscale, const float* bias, float alpha, int D,
+                                  int kslot, int n_chunks, float* ps, int* pi, void* stream) {
+  if (D % (2 * BK) != 0 || D > 1024 || nq <= 0 || nrows <= 0 || S <= 0 || n_chunks <= 0) return (int)hipErrorInvalidValue;
+  if (ldx % 16 != 0 || ldq % 16 != 0 || ldx < D || ldq < D || ((uintptr_t)X8 | (uintptr_t)Q8) % 16 != 0)
+    return (int)hipErrorInvalidValue;
+  if (!rscale || !qscale) return (int)hipErrorInvalidValue;
+  hipStream_t st = (hipStream_t)stream;
+  const int ns = (int)(((long)nrows + S - 1) / S);
+  const int n_qblocks = (nq + BN - 1) / BN;
+  const int rows_per_chunk = ((ns + n_chunks - 1) / n_chunks + BM - 1) / BM * BM;
+  n_chunks = (ns + rows_per_chunk - 1) / rows_per_chunk;
+  dim3 grid(n_qblocks * n_chunks);
+#define LZK_SGO(KK, B) do { \
+  size_t lds = (size_t)2 * 2 * TILE_ELEMS * sizeof(u16) + 2 * BM * 8; \
+  if ((size_t)BN * 4 * KK * 8 > lds) lds = (size_t)BN * 4 * KK * 8; \
+  (void)hipFuncSetAttribute((const void*)sample_topk_i8_kernel<KK, B>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+  hipLaunchKernelGGL((sample_topk_i8_kernel<KK, B>), grid, dim3(NT), lds, st, (const int8_t*)X8, ldx, ns, S, \
+                     (const int8_t*)Q8, ldq, nq, rscale, qscale, bias, alpha, D, rows_per_chunk, n_chunks, n_qblocks, \
+                     ps, pi); } while (0)
+#define LZK_SKS(KK) if (bias) LZK_SGO(KK, true); else LZK_SGO(KK, false); break
+  switch (kslot) {
+    case 1: LZK_SKS(1);
+    case 2: LZK_SKS(2);
+    case 4: LZK_SKS(4);
+    case 8: LZK_SKS(8);
+    case 10: LZK_SKS(10);
+    case 16: LZK_SKS(16);
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef LZK_SKS
+#undef LZK_SGO
+  return (int)hipGetLastError();
 }
 
 static int topk_merge(const float* ps, const int* pi, int ncand, int nq, int kslot, int kout, long idx_offset,

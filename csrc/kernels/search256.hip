@@ -17,6 +17,7 @@
 // spend its registers on MFMA accumulators. A query whose list overflows its
 // capacity is flagged and recomputed by the caller with the per-lane kernel.
 #include "lzk_g256.h"
+#include "lzk_i8score.h"
 
 #include <cstdlib>
 #include <cfloat>
@@ -134,14 +135,11 @@ struct BlkCands {
   const float* qs = nullptr;
 };
 
-// Score of the int8 scan, one rounding per step whatever the surrounding code
-// lets the compiler contract: p = float(sum) * row scale (the int32 -> float
-// conversion is exact, |sum| < 2^24 for D <= 1024), score = fma(al, p, bias)
-// with al = alpha * query scale. Every int8 epilogue (OPT 24, the tiered
-// prefilter of OPT bit 6, the dual scan) takes its scores from these two, so
-// the schedules append bit-identical records.
-__device__ __forceinline__ float i8_prod(int v, float rs) { return __fmul_rn((float)v, rs); }
-__device__ __forceinline__ float i8_score(float al, float p, float b) { return __fmaf_rn(al, p, b); }
+// Score of the int8 scan: i8_prod / i8_score of lzk_i8score.h. Every int8
+// epilogue (OPT 24, the tiered prefilter of OPT bit 6, the dual scan) takes
+// its scores from these two, so the schedules append bit-identical records --
+// and the threshold sample (search.hip sample_topk_i8_kernel) sees the scan's
+// own scores.
 
 // DUAL: one GEMM pass serves two searches of the same queries -- list A keeps
 // every row with score >= thr[q] (no label filter), list B keeps rows whose

@@ -208,6 +208,14 @@ def _flat_topk_lane(X, Q, k, kslot, bias, row_label, q_label, alpha, idx_offset,
                                  _lib.ptr(bias), _lib.ptr(row_label), _lib.ptr(q_label),
                                  float(alpha), D, kslot, nch, ps.data_ptr(), pi.data_ptr(), st)
     _lib.check(rc, "lzk_flat_topk_partial")
+    return _merge_partials(ps, pi, nch, nq, kslot, k, idx_offset)
+
+
+def _merge_partials(ps, pi, nch, nq, kslot, k, idx_offset):
+    """Per-(query, chunk) partial lists [nq, nch, kslot] -> the top-k per query."""
+    L = _lib.lib()
+    dev = ps.device
+    st = _lib.stream_ptr(dev)
     ncand = nch * kslot
     G = _merge_groups(nq, nch)
     if G > 1:
@@ -416,9 +424,10 @@ def bf16_rows(X32: torch.Tensor, Dp: int) -> torch.Tensor:
 class LeanRows:
     """The fp32 rows of a lean tenant (no bf16 copy kept in HBM) standing in
     for the bf16 operand of the int8 search paths: a slice converts on the fly
-    (bf16, zero-padded to Dp -- the 1/S threshold sample and the rare overflow
-    fallback); the re-score above the error cut reads the fp32 rows and the
-    fp32 queries ``Q32`` directly (lzk_cand_rescore32)."""
+    (bf16, zero-padded to Dp -- the rare overflow fallback, and the 1/S
+    threshold sample only with ``I8_SAMPLE`` off); the re-score above the
+    error cut reads the fp32 rows and the fp32 queries ``Q32`` directly
+    (lzk_cand_rescore32)."""
     dtype = torch.bfloat16
     CHUNK = 1 << 20  # rows per converted block of the overflow fallback
 
@@ -579,6 +588,52 @@ def i8_query(q16: torch.Tensor, d: int, sumsq: torch.Tensor, n_sumsq: int, smax:
     return q8, qs, margin, margin_rig
 
 
+# The store search's threshold sample on the int8 MFMA (sample_topk_i8);
+# LZK_I8_SAMPLE=0 (or I8_SAMPLE = False) keeps the bf16 lane kernel over
+# X16[::S]: the A/B arm and the tests' reference.
+I8_SAMPLE = os.environ.get("LZK_I8_SAMPLE", "1") != "0"
+_lib.register("lzk_sample_topk_i8", _lib.I, [_lib.P, _lib.L, _lib.I, _lib.I, _lib.P, _lib.L, _lib.I, _lib.P, _lib.P,
+                                             _lib.P, _lib.F, _lib.I, _lib.I, _lib.I, _lib.P, _lib.P, _lib.P])
+
+
+def sample_topk_i8(X8: torch.Tensor, rscale: torch.Tensor, Q8: torch.Tensor, qscale: torch.Tensor, kslot: int,
+                   S: int, *, bias=None, alpha: float = 1.0, n_chunks: int = None):
+    """Per-query top-``kslot`` of the int8 scan's score over the rows 0, S,
+    2S, ... of ``X8`` [N, Dp], read in place (search.hip
+    sample_topk_i8_kernel: no gathered copy of rows, scales or bias). The
+    score of row r for query q is the scan's, bit for bit:
+    ``fma(alpha * qscale[q], fl(float(<X8[r], Q8[q]>) * rscale[r]), bias[r])``.
+    ``n_chunks``: row chunks of the sample (whole 128-row tiles; default: enough
+    workgroups to fill the device). Returns (scores fp32 [nq, kslot]
+    descending, -inf padded; rows int64 [nq, kslot], -1 padded, equal scores
+    by ascending row)."""
+    L = _lib.lib()
+    nq, Dp = Q8.shape
+    N = X8.shape[0]
+    dev = X8.device
+    assert X8.dtype == torch.int8 and Q8.dtype == torch.int8 and Dp % 128 == 0 and Dp <= 1024 and X8.shape[1] == Dp
+    assert X8.stride(1) == 1 and Q8.stride(1) == 1 and N > 0 and nq > 0 and S >= 1
+    assert rscale.dtype == torch.float32 and rscale.stride(0) == 1 and rscale.shape[0] >= N
+    assert bias is None or (bias.dtype == torch.float32 and bias.stride(0) == 1 and bias.shape[0] >= N)
+    qs = qscale.contiguous()
+    assert qs.dtype == torch.float32 and qs.shape[0] == nq
+    ns = -(-N // S)
+    if n_chunks:
+        # same normalisation as the C launcher: chunks are whole 128-row tiles
+        rpc = -(-(-(-ns // n_chunks)) // 128) * 128
+        nch = -(-ns // rpc)
+    else:
+        nch = L.lzk_flat_topk_chunks(ns, nq, TARGET_WGS)
+    part = nq * nch * kslot
+    ws = _ws.get(dev, part * 8)
+    ps = ws[: part * 4].view(torch.float32)
+    pi = ws[part * 4: part * 8].view(torch.int32)
+    _lib.check(L.lzk_sample_topk_i8(X8.data_ptr(), X8.stride(0), N, int(S), Q8.data_ptr(), Q8.stride(0), nq,
+                                    rscale.data_ptr(), qs.data_ptr(), _lib.ptr(bias), float(alpha), Dp, kslot, nch,
+                                    ps.data_ptr(), pi.data_ptr(), _lib.stream_ptr(dev)), "lzk_sample_topk_i8")
+    return _merge_partials(ps, pi, nch, nq, kslot, kslot, 0)
+
+
 def flat_topk_i8(X8: torch.Tensor, rscale: torch.Tensor, Q8: torch.Tensor, qscale: torch.Tensor,
                  X16: torch.Tensor, Q16: torch.Tensor, k: int, *, bias=None, alpha: float = 1.0, margin=None,
                  margin_rig=None):
@@ -593,8 +648,10 @@ def flat_topk_i8(X8: torch.Tensor, rscale: torch.Tensor, Q8: torch.Tensor, qscal
     difference for every row (TenantGraph: the worst case of every term; when
     omitted, ``margin`` is taken as the bound). The result always equals the
     bf16 scan's:
-      1. thr = bf16 sample bound - margin: tau = the 1/S sample's SPEC_J-th best
-         (speculative) or k-th best; the int8 scan keeps every row whose int8
+      1. thr = sample bound - margin: tau = the 1/S sample's SPEC_J-th best
+         (speculative) or k-th best, by the scan's own int8 score
+         (:func:`sample_topk_i8`; ``I8_SAMPLE`` off: by bf16 score, the lane
+         kernel over ``X16[::S]``); the int8 scan keeps every row whose int8
          score clears thr;
       2. cut = (k-th best int8 score of the list) - 2 * margin_rig: a row of
          the true top-k has int8 score >= T - m >= that cut (T the true k-th
@@ -607,6 +664,11 @@ def flat_topk_i8(X8: torch.Tensor, rscale: torch.Tensor, Q8: torch.Tensor, qscal
          optimistic -- is recomputed by the exact bf16 fallback, as is a list
          that overflowed;
       4. exact select.
+    Exactness does not depend on where tau comes from: thr only decides which
+    rows the scan lists, and steps 2-4 hold for ANY thr -- the certificate
+    level is thr + margin_rig whatever thr is, and a query it does not certify
+    goes to the exact fallback. So the sample needs neither bf16 precision nor
+    the bf16 rows; a lean tenant converts nothing for it.
     Returns (scores fp32 [nq, k], rows int64 [nq, k]) like :func:`flat_topk`."""
     L = _lib.lib()
     nq, Dp = Q16.shape
@@ -623,12 +685,15 @@ def flat_topk_i8(X8: torch.Tensor, rscale: torch.Tensor, Q8: torch.Tensor, qscal
     S = max(1, min(CAND_STRIDE_NARROW if narrow else CAND_STRIDE, N // max(16 * kslot, 1)))
     J = SPEC_J_NARROW if narrow else SPEC_J
     spec = 0 < J < k and S >= SPEC_MIN_STRIDE
-    # the 1/S sample's top-kslot (lane kernel); speculative threshold: its
+    # the 1/S sample's top-kslot (int8 sample kernel); speculative threshold: its
     # J-th best (~J * S-th overall) instead of its k-th -- lists ~k / J times
     # shorter; the certificate sends a query whose threshold was too high to
     # the exact fallback
-    bs = bias[:N:S].contiguous() if bias is not None else None
-    ts, _ = _flat_topk_lane(X16[::S], Q16, kslot, kslot, bs, None, None, alpha, 0, None)
+    if I8_SAMPLE:
+        ts, _ = sample_topk_i8(X8[:N], rscale, Q8, qscale, kslot, S, bias=bias, alpha=alpha)
+    else:
+        bs = bias[:N:S].contiguous() if bias is not None else None
+        ts, _ = _flat_topk_lane(X16[::S], Q16, kslot, kslot, bs, None, None, alpha, 0, None)
     # narrow batches scan at HBM speed with a worst-case margin by default:
     # longer lists (a few thousand rows per query) cost next to nothing there
     cap = max(NARROW_CAP if narrow else 2048, 16 * kslot * S)
