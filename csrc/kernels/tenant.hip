@@ -453,7 +453,8 @@ __global__ __launch_bounds__(256) void store_rerank_kernel(const float* __restri
     const float s2 = __shfl(my_s, o, 64);
     const long r2 = __shfl(my_r, o, 64);
     const bool l2 = r2 >= 0 && s2 != LZK_NEG_INF;
-    if (l2 && o != lane && (s2 > my_s || (s2 == my_s && r2 < my_r))) ++rank;
+    // equal (score, row) pairs (a row listed twice) keep their slot order
+    if (l2 && o != lane && (s2 > my_s || (s2 == my_s && (r2 < my_r || (r2 == my_r && o < lane))))) ++rank;
   }
   const int nlive = __popcll(__ballot(live));
   if (live && rank < k) {
@@ -543,7 +544,8 @@ __global__ __launch_bounds__(256) void store_rerank_block_kernel(const float* __
     const float s2 = __shfl(my_s, o, 64);
     const long r2 = __shfl(my_r, o, 64);
     const bool l2 = r2 >= 0 && s2 != LZK_NEG_INF;
-    if (l2 && o != lane && (s2 > my_s || (s2 == my_s && r2 < my_r))) ++rank;
+    // equal (score, row) pairs (a row listed twice) keep their slot order
+    if (l2 && o != lane && (s2 > my_s || (s2 == my_s && (r2 < my_r || (r2 == my_r && o < lane))))) ++rank;
   }
   const int nlive = __popcll(__ballot(live));
   if (live && rank < k) {

@@ -120,18 +120,28 @@ def components_sel(src: torch.Tensor, dst: torch.Tensor, n: int, w: Optional[tor
 
 
 def pairs_above(X: torch.Tensor, tau: float, max_pairs: int = 1 << 22) -> torch.Tensor:
-    """K7: all (i<j) with <x_i,x_j> > tau, sorted by (i, j). X bf16 [n, D%64==0] on GPU."""
+    """K7: all (i<j) with <x_i,x_j> > tau, sorted by (i, j). X bf16 [n, D%64==0] on GPU.
+    ``max_pairs`` sizes the first launch's buffer, not the result: the kernel
+    counts every pair, so an overflowing call runs once more with a buffer of
+    that count and the complete set comes back either way."""
     n = X.shape[0]
     if not X.is_cuda:
         S = X.float() @ X.float().T
         iu = torch.triu_indices(n, n, 1)
         m = S[iu[0], iu[1]] > tau
         return torch.stack([iu[0][m], iu[1][m]], 1).to(torch.int32)
-    cnt = torch.zeros(1, dtype=torch.int32, device=X.device)
-    out = torch.empty((max_pairs, 2), dtype=torch.int32, device=X.device)
-    _lib.check(_lib.lib().lzk_pairs_above(X.data_ptr(), X.stride(0), n, X.shape[1], float(tau), cnt.data_ptr(),
-                                          max_pairs, out.data_ptr(), _st(X)), "pairs_above")
-    k = min(int(cnt.item()), max_pairs)
+    cap = max(1, int(max_pairs))
+    for _ in range(2):
+        cnt = torch.zeros(1, dtype=torch.int32, device=X.device)
+        out = torch.empty((cap, 2), dtype=torch.int32, device=X.device)
+        _lib.check(_lib.lib().lzk_pairs_above(X.data_ptr(), X.stride(0), n, X.shape[1], float(tau), cnt.data_ptr(),
+                                              cap, out.data_ptr(), _st(X)), "pairs_above")
+        k = int(cnt.item())
+        if k <= cap:
+            break
+        cap = k  # the pairs past the buffer were counted, not kept: once more with room for all of them
+    else:
+        raise RuntimeError(f"pairs_above: {k} pairs after a launch sized for {cap}")
     p = out[:k].long()
     o = torch.argsort(p[:, 0] * n + p[:, 1])
     return p[o].to(torch.int32)

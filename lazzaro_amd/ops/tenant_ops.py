@@ -695,7 +695,8 @@ def store_rerank(Qf: torch.Tensor, X: torch.Tensor, sqn: torch.Tensor, bias: tor
     """Exact fp32 re-rank of store-search candidates in one launch
     (tenant.hip store_rerank_kernel): scores of the rows ``cand`` [M, C]
     (C <= 64, -1 = empty) against ``Qf`` [M, D], top-k by (score desc, row
-    asc). Returns (scores [M, k], rows int64 [M, k]; -inf / -1 padding);
+    asc; a row listed twice is kept twice, like the torch tier keeps it).
+    Returns (scores [M, k], rows int64 [M, k]; -inf / -1 padding);
     with ``kind`` (the graph's kind column) the rows that are not graph
     nodes come back as -1 (the search_memories view), in the same launch."""
     M, C = cand.shape
