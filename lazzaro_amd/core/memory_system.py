@@ -233,7 +233,8 @@ class MemorySystem(ConsolidationMixin):
             emb = OnDeviceEmbedder(cfg.embed_model, device=cfg.device, weights=cfg.embed_weights)
         kw.setdefault("index", cfg.index)
         kw.setdefault("index_params", {"nlist": cfg.nlist, "nprobe": cfg.nprobe, "pq_m": cfg.pq_m,
-                                       "ivf_min_rows": cfg.ivf_min_rows, "ivf_filtered": cfg.ivf_filtered})
+                                       "ivf_min_rows": cfg.ivf_min_rows, "ivf_filtered": cfg.ivf_filtered,
+                                       "wide_k": cfg.wide_k})
         kw.setdefault("hierarchy_mode", cfg.hierarchy_mode)
         kw.setdefault("hierarchy_params", {"fine": cfg.hierarchy_fine, "top": cfg.hierarchy_top,
                                            "every": cfg.hierarchy_every})
@@ -848,7 +849,8 @@ class MemorySystem(ConsolidationMixin):
                 "filtered_searches": g.filtered_searches, "filter_plans_built": g.filter_plans_built,
                 "filtered_sparse": g.filtered_sparse, "filtered_ann": g.filtered_ann,
                 "mmr_searches": g.mmr_searches, "expanded_searches": g.expanded_searches,
-                "boosted_searches": g.boosted_searches, "boost_columns_built": g.boost_columns_built, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
+                "boosted_searches": g.boosted_searches, "boost_columns_built": g.boost_columns_built,
+                "wide_searches": g.wide_searches, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
                 "avg_search_batch_ms": round(sms / m["search_batches"], 3) if m.get("search_batches") else 0.0}
 
     def _graph_bytes(self) -> int:

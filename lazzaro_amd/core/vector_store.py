@@ -55,16 +55,19 @@ class HBMStore:
     def __init__(self, db_dir: str = "db", device=None, metric: str = "l2",
                  consistency_interval: float = 0.5, keep_fp32: bool = True, index: str = "flat",
                  nlist: int = 4096, nprobe: int = 32, pq_m: int = 64, ivf_min_rows: int = 1_000_000,
-                 ivf_filtered: bool = False):
+                 ivf_filtered: bool = False, wide_k: bool = False):
         """index="ivfpq": a tenant arena with >= ivf_min_rows live rows is served
         by IVF-PQ candidates re-ranked exactly (smaller tenants stay exact flat).
         ivf_filtered: an attached tenant graph's filtered searches (``where=``)
         may use the index too, scanning only the passing rows of the probed
-        lists (TenantGraph._store_search_where); off: they take the flat routes."""
+        lists (TenantGraph._store_search_where); off: they take the flat routes.
+        wide_k: an attached tenant graph serves searches with 16 < k <= 64 on the
+        certified int8 candidate route (TenantGraph.wide_k); off: the exact fp32 scan."""
         if index not in ("flat", "ivfpq"):
             raise ValueError("index must be 'flat' or 'ivfpq'")
         self.index, self.ivf_params = index, dict(nlist=nlist, nprobe=nprobe, m=pq_m, min_rows=ivf_min_rows)
         self.ivf_filtered = bool(ivf_filtered)
+        self.wide_k = bool(wide_k)
         self.db_dir = db_dir
         self._uri = os.path.join(db_dir, "lancedb")
         os.makedirs(self._uri, exist_ok=True)
@@ -90,6 +93,8 @@ class HBMStore:
             self._graphs[user_id] = graph
             self._arenas.pop(user_id, None)
             self._synced.pop(user_id, None)
+            if self.wide_k:
+                graph.wide_k = True
             if self.index == "ivfpq":  # large tenants: IVF-PQ candidates + exact fp32 re-rank on the graph
                 graph.ann_cfg = dict(self.ivf_params, filtered=self.ivf_filtered)
 

@@ -80,6 +80,9 @@ MAX_ETYPES = TYPE_MASK + 1
 # below this many query x row products the exact float64 GEMM is used directly
 KERNEL_MIN_WORK = 1 << 22
 CAND_SLOTS = 16  # candidates per query from the bf16 scan before the exact re-rank
+# TenantGraph.wide_k: a store search with CAND_SLOTS < k <= WIDE_CAND_SLOTS takes the certified
+# int8 route with WIDE_CAND_SLOTS candidates (ops/search.py flat_topk_i8_wide) instead of _exact_store
+WIDE_CAND_SLOTS = 64
 # fp8 candidate scan of the store search: large batches over large tenants
 # (the candidate kernel's regime), margin in standard deviations of the fp8
 # score error (see TenantGraph._fp8_candidates)
@@ -2864,7 +2867,41 @@ class TenantGraph:
             else:
                 _, cand = flat_topk(self.emb16[:n], q16, kc, bias=bias, alpha=alpha)
             return self._rerank_store(Qf, cand, k, metric, bias, node_rows)
+        if self._wide_route(k, M, metric):
+            # 64 bf16 candidates from the certified int8 scan, then the fp32 re-rank: the k <= 16
+            # contract with kc = 64 (at k = 64 the re-rank has no bf16 headroom left)
+            self.wide_searches += 1
+            _, cand = self._i8_candidates_wide(Qf, self._q16(Qf), WIDE_CAND_SLOTS, bias, alpha)
+            return self._rerank_store(Qf, cand, k, metric, bias, node_rows)
         return self._exact_store(Qf, k, metric, bias)
+
+    wide_k = False  # opt-in (HBMStore(wide_k=True) / MemoryConfig.wide_k): see _wide_route
+    wide_searches = 0
+
+    def _wide_route(self, k: int, M: int, metric: str) -> bool:
+        """Whether a store search with ``k`` > CAND_SLOTS leaves ``_exact_store``
+        for the wide int8 route: ``wide_k`` set, k <= WIDE_CAND_SLOTS, and a
+        tenant that :meth:`_store_search` would send to :meth:`_i8_candidates`
+        at k <= 16 -- on the GPU, int8 scan copy, unit rows, at least
+        LOWP_MIN_ROWS rows, a batch of LOWP_MIN_Q queries or the narrow scan,
+        bf16 rows kept (not lean). Everything else keeps today's code."""
+        if not (self.wide_k and CAND_SLOTS < k <= WIDE_CAND_SLOTS and self.on_gpu):
+            return False
+        if self.lean or self.emb8 is None or self.emb8.dtype != torch.int8 or self.emb16 is None:
+            return False
+        return bool(self.unit_rows() and self.n >= LOWP_MIN_ROWS and (M >= LOWP_MIN_Q or LOWP_NARROW))
+
+    def _i8_candidates_wide(self, Qf: torch.Tensor, q16: torch.Tensor, kc: int, bias: torch.Tensor, alpha: float):
+        """:meth:`_i8_candidates` for 16 < kc <= 64 (ops.search.flat_topk_i8_wide),
+        under the same two margins."""
+        from ..ops.search import NARROW_MAX_Q, flat_topk_i8_wide
+        q8, qs, margin, margin_rig = self._i8_query(q16, alpha)
+        if not self._lowp_exact(Qf.shape[0] < NARROW_MAX_Q):
+            margin_rig = margin
+        else:
+            margin = margin_rig
+        return flat_topk_i8_wide(self.emb8, self.rs8, q8, qs, self._scan_rows(self.n, Qf), q16, kc, bias=bias,
+                                 alpha=alpha, margin=margin, margin_rig=margin_rig)
 
     def _ann_candidates(self, Qf: torch.Tensor, R: int, cfg: Dict, plan=None) -> torch.Tensor:
         """Graph rows [M, R] from the tenant's IVF-PQ index, built on first

@@ -18,6 +18,7 @@ Results are ordered by (score desc, row asc); missing slots are (-inf, -1).
 """
 from __future__ import annotations
 
+import math
 import os
 
 import numpy as np
@@ -723,6 +724,226 @@ def flat_topk_i8(X8: torch.Tensor, rscale: torch.Tensor, Q8: torch.Tensor, qscal
                                      cs.data_ptr(), ci.data_ptr(), None, None, None, st), "lzk_cand_gather")
     _rescore_above_cut(X16, Q16, k, kslot, bias, alpha, margin_rig, cnt, cs, ci, cap, chk=chk)
     return _select_with_fallback(X16, Q16, k, kslot, bias, None, None, alpha, 0, cnt, cs, ci, cap, need=need)
+
+
+# ---- wide k (17 .. 64): csrc/kernels/widek.hip
+_lib.register("lzk_cand_select_wide", _lib.I, [_lib.P, _lib.P, _lib.P, _lib.I, _lib.I, _lib.I, _lib.L, _lib.P, _lib.P,
+                                               _lib.P, _lib.P, _lib.P, _lib.P])
+_lib.register("lzk_flat_topk_wide_chunks", _lib.I, [_lib.I, _lib.I])
+_lib.register("lzk_flat_topk_wide", _lib.I, [_lib.P, _lib.L, _lib.I, _lib.P, _lib.L, _lib.I, _lib.P, _lib.F, _lib.I,
+                                             _lib.I, _lib.P, _lib.P, _lib.I, _lib.L, _lib.P, _lib.P, _lib.P])
+_lib.register("lzk_flat_topk_wide_masked", _lib.I, [_lib.P, _lib.L, _lib.I, _lib.P, _lib.L, _lib.I, _lib.P, _lib.F,
+                                                    _lib.I, _lib.I, _lib.P, _lib.P, _lib.I, _lib.L, _lib.P, _lib.P,
+                                                    _lib.P, _lib.P])
+
+WIDE_K_MAX = 64            # results the wide kernels keep per query
+WIDE_P_FALLBACK = 1e-4     # share of queries the threshold rule may send to the exact fallback
+WIDE_J = None              # tests: force the sample rank of the threshold
+WIDE_CAP_MIN = 2048        # list capacity of a wide batch (narrow: NARROW_CAP)
+WIDE_LIST_FACTOR = 16      # list capacity = this many times the expected j * S entries
+_ws_wide = _Workspace()
+
+
+def wide_spec_j(k: int, S: int, p_max: float = WIDE_P_FALLBACK) -> int:
+    """The sample rank of :func:`flat_topk_i8_wide`'s threshold: the smallest
+    j <= 16 with P(Binomial(k, 1/S) >= j) <= p_max, 16 when there is none (a
+    small store, S near 1: most queries then take the exact fallback).
+
+    A row is in the 1/S sample with probability 1/S, so the number of a
+    query's true top-k rows inside the sample is Binomial(k, 1/S); when at
+    least j of them are, the sample's j-th best lies at or above the k-th
+    score and the certificate sends the query to the fallback."""
+    k, S = int(k), max(int(S), 1)
+    p = 1.0 / S
+    for j in range(1, 17):
+        tail = sum(math.comb(k, i) * p ** i * (1.0 - p) ** (k - i) for i in range(j, k + 1))
+        if tail <= p_max:
+            return j
+    return 16
+
+
+def _wide_chunks(N: int, nq: int, n_chunks=None) -> int:
+    """Row chunks of the wide exact kernel: 8,192 rows each, at most 256 --
+    and at most 65,536 / nq (>= 8), which keeps the partial lists [nq, chunks,
+    64] within 32 MB however wide the batch."""
+    hint = int(n_chunks) if n_chunks else min(-(-N // 8192), max(8, min(256, 65536 // max(nq, 1))))
+    return _lib.lib().lzk_flat_topk_wide_chunks(int(N), max(hint, 1))
+
+
+def _flat_topk_wide(X16, Q16, k, bias, alpha, idx_offset=0, n_chunks=None, q_active=None, out=None):
+    """lzk_flat_topk_wide[_masked]: the partial pass over (query, row chunk)
+    and the merge; with ``q_active`` (int32 [nq]) only the flagged queries'
+    rows of ``out`` = (scores [nq, k], rows [nq, k]) are written."""
+    L = _lib.lib()
+    nq, D = Q16.shape
+    N = X16.shape[0]
+    dev = X16.device
+    assert X16.dtype == torch.bfloat16 and Q16.dtype == torch.bfloat16 and 1 <= k <= WIDE_K_MAX
+    assert X16.shape[1] == D and D % 8 == 0 and D <= 2048 and X16.stride(1) == 1 and Q16.stride(1) == 1
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.shape[0] >= N)
+    if out is None:
+        assert q_active is None
+        out = (torch.empty((nq, k), dtype=torch.float32, device=dev), torch.empty((nq, k), dtype=torch.long, device=dev))
+    os_, oi = out
+    nch = _wide_chunks(N, nq, n_chunks)
+    part = nq * nch * WIDE_K_MAX
+    ws = _ws_wide.get(dev, part * 8)
+    ps = ws[: part * 4].view(torch.float32)
+    pi = ws[part * 4: part * 8].view(torch.int32)
+    args = (X16.data_ptr(), X16.stride(0), N, Q16.data_ptr(), Q16.stride(0), nq, _lib.ptr(bias), float(alpha), D,
+            nch, ps.data_ptr(), pi.data_ptr(), int(k), int(idx_offset), os_.data_ptr(), oi.data_ptr())
+    if q_active is None:
+        _lib.check(L.lzk_flat_topk_wide(*args, _lib.stream_ptr(dev)), "lzk_flat_topk_wide")
+    else:
+        assert q_active.dtype == torch.int32 and q_active.shape[0] == nq
+        _lib.check(L.lzk_flat_topk_wide_masked(*args, q_active.data_ptr(), _lib.stream_ptr(dev)),
+                   "lzk_flat_topk_wide_masked")
+    return os_, oi
+
+
+def flat_topk_wide(X16: torch.Tensor, Q16: torch.Tensor, k: int, *, bias=None, alpha: float = 1.0,
+                   idx_offset: int = 0, n_chunks: int = None):
+    """Exact top-k (k <= 64) of ``alpha * <Q16, X16> + bias`` over all bf16
+    rows, ordered by (score desc, row asc), (-inf, -1) past the live rows
+    (widek.hip flat_topk_wide_kernel + the wide select as merge). The wide
+    counterpart of the lane kernel: the exact fallback of
+    :func:`flat_topk_i8_wide`, rare there, so built for correctness without a
+    host read first and for speed second (one query per block, 8 lanes per
+    row). D % 8 == 0, D <= 2048. CPU tensors: ``_ref_topk``."""
+    if Q16.dim() == 1:
+        Q16 = Q16[None, :]
+    if not X16.is_cuda:
+        return _ref_topk(X16, Q16, k, bias, None, None, alpha, idx_offset)
+    nq = Q16.shape[0]
+    if X16.shape[0] == 0 or nq == 0:
+        return (torch.full((nq, k), float("-inf"), device=X16.device),
+                torch.full((nq, k), -1, dtype=torch.long, device=X16.device))
+    return _flat_topk_wide(X16, Q16, k, bias, alpha, idx_offset, n_chunks)
+
+
+def cand_select_wide(cnt, cs, ci, cap: int, kout: int, *, idx_offset: int = 0, need=None, q_active=None, out=None):
+    """lzk_cand_select_wide: per query the ``kout`` <= 64 best of the first
+    min(cnt & 0x3fffffff, cap) entries of its list ``cs`` / ``ci`` [nq, cap]
+    (``cnt`` None: cap entries each) by (score desc, row asc); -inf entries
+    select as (-inf, -1). Returns (scores [nq, kout], rows int64 [nq, kout] +
+    idx_offset, ovf int32 [nq] = cnt > cap or cnt < need[q])."""
+    nq = cs.shape[0] if cs.dim() == 2 else cs.numel() // cap
+    dev = cs.device
+    if out is None:
+        out = (torch.empty((nq, kout), dtype=torch.float32, device=dev),
+               torch.empty((nq, kout), dtype=torch.long, device=dev))
+    ovf = torch.empty((nq,), dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().lzk_cand_select_wide(_lib.ptr(cnt), cs.data_ptr(), ci.data_ptr(), int(cap), nq, int(kout),
+                                               int(idx_offset), out[0].data_ptr(), out[1].data_ptr(), ovf.data_ptr(),
+                                               _lib.ptr(need), _lib.ptr(q_active), _lib.stream_ptr(dev)),
+               "lzk_cand_select_wide")
+    return out[0], out[1], ovf
+
+
+def flat_topk_i8_wide(X8: torch.Tensor, rscale: torch.Tensor, Q8: torch.Tensor, qscale: torch.Tensor,
+                      X16: torch.Tensor, Q16: torch.Tensor, k: int, *, bias=None, alpha: float = 1.0, margin=None,
+                      margin_rig=None):
+    """:func:`flat_topk_i8` for 17 <= k <= 64: same arguments, same result
+    (the bf16 scan's top-k, exactly), same scan kernels. Only the stages that
+    hold 16 register slots per lane are replaced:
+
+      1. sample: :func:`sample_topk_i8` with 16 slots at stride S;
+      2. threshold: tau = the sample's j-th best (``lzk_thr_prep``), thr =
+         tau - margin. The result is exact for ANY thr (steps 2-4 of
+         :func:`flat_topk_i8`); j only trades list length (~j * S rows) against
+         the share of queries sent to the fallback: a query needs it roughly
+         when at least j of its true top-k rows fall in the sample, a
+         Binomial(k, 1/S) count. j is the smallest rank <= 16 with
+         P(Binomial(k, 1/S) >= j) <= 1e-4 (:func:`wide_spec_j`, computed from
+         k and S on the host). At S = 64:
+             k = 17 .. 30: j = 5     k = 31 .. 47: j = 6     k = 48 .. 64: j = 7
+      3. the list capacity and the scan's record buffers are sized from j * S;
+      4. scan: the unchanged int8 kernels with that thr;
+      5. cut: the k best by int8 score (``lzk_cand_select_wide``) scored
+         exactly, their minimum (``lzk_cand_cut``: one wave per query for
+         k > 16);
+      6. re-score and certificate: ``lzk_cand_rescore`` with k_need = k at the
+         level thr + margin_rig;
+      7. select: ``lzk_cand_select_wide``;
+      8. fallback: ``lzk_flat_topk_wide_masked`` on the overflow / certificate
+         flags, no host read.
+    bf16 rows only (no ``LeanRows``). CPU tensors: ``_ref_topk``.
+    Returns (scores fp32 [nq, k], rows int64 [nq, k])."""
+    k = int(k)
+    assert 16 < k <= WIDE_K_MAX, "flat_topk_i8_wide serves 17 <= k <= 64 (flat_topk_i8 below)"
+    if not X16.is_cuda:
+        return _ref_topk(X16, Q16, k, bias, None, None, alpha, 0)
+    L = _lib.lib()
+    nq, Dp = Q16.shape
+    N = X16.shape[0]
+    kslot = 16
+    assert X8.dtype == torch.int8 and Q8.dtype == torch.int8 and Dp % 128 == 0 and Dp <= 1024
+    assert X8.shape[1] == Dp and X8.stride(1) == 1 and Q8.stride(1) == 1 and X8.shape[0] >= N
+    assert rscale.dtype == torch.float32 and qscale.dtype == torch.float32 and rscale.shape[0] >= N
+    assert alpha > 0 and not isinstance(X16, LeanRows)
+    dev = X16.device
+    st = _lib.stream_ptr(dev)
+    if margin_rig is None:
+        margin_rig = margin  # (None: no bound known -- every list entry is re-scored)
+    narrow = nq < NARROW_MAX_Q and SCAN8_NARROW and Dp % 64 == 0
+    S = max(1, min(CAND_STRIDE_NARROW if narrow else CAND_STRIDE, N // max(16 * kslot, 1)))
+    j = int(WIDE_J) if WIDE_J else wide_spec_j(k, S)
+    ts, _ = sample_topk_i8(X8[:N], rscale, Q8, qscale, kslot, S, bias=bias, alpha=alpha)
+    cap = max(NARROW_CAP if narrow else WIDE_CAP_MIN, WIDE_LIST_FACTOR * j * S, WIDE_K_MAX)
+    cnt, cs, ci = _cand_lists(dev, nq, cap, 0, zero=False)
+    thr = torch.empty(nq, dtype=torch.float32, device=dev)
+    cert = torch.empty(nq, dtype=torch.float32, device=dev)
+    mg = margin.float().contiguous() if margin is not None else None
+    mr = margin_rig.float().contiguous() if margin_rig is not None else None
+    _lib.check(L.lzk_thr_prep(ts.data_ptr(), ts.stride(0), j - 1, _lib.ptr(mg), _lib.ptr(mr), nq, thr.data_ptr(),
+                              cert.data_ptr(), cnt.data_ptr(), st), "lzk_thr_prep")
+    qs = qscale.contiguous()
+    need = torch.empty(nq, dtype=torch.int32, device=dev)
+    if narrow:
+        _scan8_narrow(X8[:N], rscale[:N], Q8, qs, bias, alpha, thr, j, 2 * S, cap, (cnt, cs, ci))
+    else:
+        grid = L.lzk_cand_grid_f8(N, nq)
+        bbuf, bcap, bcnt = _blk_records(dev, grid, nq, j, 2 * S, 1)
+        _lib.check(L.lzk_flat_cand_i8(X8.data_ptr(), X8.stride(0), N, Q8.data_ptr(), Q8.stride(0), nq, Dp,
+                                      _lib.ptr(bias), rscale.data_ptr(), qs.data_ptr(), float(alpha), thr.data_ptr(),
+                                      cap, cnt.data_ptr(), cs.data_ptr(), ci.data_ptr(), bbuf.data_ptr(), bcap,
+                                      bcnt.data_ptr(), st), "lzk_flat_cand_i8")
+        _lib.check(L.lzk_cand_gather(bbuf.data_ptr(), bcap, bcnt.data_ptr(), grid, cap, nq, cnt.data_ptr(),
+                                     cs.data_ptr(), ci.data_ptr(), None, None, None, st), "lzk_cand_gather")
+    _rescore_above_cut_wide(X16, Q16, k, bias, alpha, mr, cnt, cs, ci, cap, (cert, k, cap + 1, need))
+    return _select_with_fallback_wide(X16, Q16, k, bias, alpha, cnt, cs, ci, cap, need=need)
+
+
+def _rescore_above_cut_wide(X16, Q16, k, bias, alpha, margin, cnt, cs, ci, cap, chk):
+    """:func:`_rescore_above_cut` for k > 16: the k best list entries by int8
+    score come from the wide select, their exact minimum from the wave
+    ``cand_cut_kernel`` (generic in k; lzk_cand_cut launches it for k > 16)."""
+    L = _lib.lib()
+    nq, Dp = Q16.shape
+    dev = Q16.device
+    st = _lib.stream_ptr(dev)
+    tau, k_need, need_val, need = chk
+    cut = None
+    if margin is not None:
+        _, i8, _ = cand_select_wide(cnt, cs, ci, cap, k)
+        cut = torch.empty(nq, dtype=torch.float32, device=dev)
+        _lib.check(L.lzk_cand_cut(X16.data_ptr(), X16.stride(0), int(X16.shape[0]), Q16.data_ptr(), Q16.stride(0),
+                                  Dp, nq, 0, _lib.ptr(bias), float(alpha), i8.data_ptr(), k, k, margin.data_ptr(),
+                                  0.0, 0, cut.data_ptr(), st), "lzk_cand_cut")
+    _lib.check(L.lzk_cand_rescore(X16.data_ptr(), X16.stride(0), Q16.data_ptr(), Q16.stride(0), nq, Dp,
+                                  _lib.ptr(bias), float(alpha), cnt.data_ptr(), cap, cs.data_ptr(), ci.data_ptr(),
+                                  _lib.ptr(cut), float("-inf"), tau.data_ptr(), int(k_need), int(need_val),
+                                  need.data_ptr(), st), "lzk_cand_rescore")
+
+
+def _select_with_fallback_wide(X16, Q16, k, bias, alpha, cnt, cs, ci, cap, need=None, ovf_sink=None):
+    """:func:`_select_with_fallback` for k > 16: the wide select, then the
+    flagged queries (list overflowed, or not certified: cnt < need[q])
+    recomputed exactly by the masked wide kernel on the device."""
+    os_, oi, ovf = cand_select_wide(cnt, cs, ci, cap, k, need=need)
+    if ovf_sink is not None:  # the caller's view of the lists: (fallback flags, list lengths)
+        ovf_sink.append((ovf, cnt))
+    return _flat_topk_wide(X16, Q16, k, bias, alpha, 0, None, q_active=ovf, out=(os_, oi))
 
 
 def _cert_tau(thr: torch.Tensor, margin_rig: torch.Tensor, floor: float = None,
