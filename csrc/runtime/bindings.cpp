@@ -325,6 +325,25 @@ PYBIND11_MODULE(_lzrt, m) {
            },
            py::arg("texts"), py::arg("max_len") = 512, py::arg("overlap") = 64);
 
+  // ---- lexical terms (keyword search) ----
+  m.def("lex_terms",
+        [](const std::vector<std::string>& texts, int slots) {
+          if (slots < 1 || slots > 64) throw std::invalid_argument("slots must be in 1 .. 64");
+          const py::ssize_t n = (py::ssize_t)texts.size();
+          py::array_t<uint32_t> a({n, (py::ssize_t)slots});
+          py::array_t<int32_t> dl(n);
+          uint32_t* ap = a.mutable_data();
+          int32_t* dp = dl.mutable_data();
+          {
+            py::gil_scoped_release r;
+            const Tokenizer tok;  // (the uncased basic split; no vocabulary is consulted)
+            for (py::ssize_t i = 0; i < n; ++i) dp[i] = lex_row(tok, texts[(size_t)i], slots, ap + i * slots);
+          }
+          return py::make_tuple(a, dl);
+        },
+        py::arg("texts"), py::arg("slots"));
+  m.def("lex_term_id", [](const std::string& w) { return lex_term_id(w); });
+
   // ---- graph host utilities ----
   m.def("build_csr",
         [](py::array_t<int32_t, py::array::c_style | py::array::forcecast> src,

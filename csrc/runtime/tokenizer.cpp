@@ -2,6 +2,7 @@
 
 #include <fstream>
 
+#include "unicode_alnum.h"
 #include "unicode_tables.h"
 
 namespace lzrt {
@@ -250,6 +251,45 @@ int Tokenizer::encode_chunks(const std::vector<std::string>& texts, int max_len,
     std::copy(wins[i].begin(), wins[i].end(), ids.begin() + i * S);
   }
   return S;
+}
+
+uint32_t lex_term_id(const std::string& word) {
+  uint32_t h = 2166136261u;
+  for (unsigned char c : word) { h ^= c; h *= 16777619u; }
+  const uint32_t t = (h ^ (h >> 24)) & 0xFFFFFFu;
+  return t ? t : 1u;
+}
+
+bool lex_is_word(const std::string& token) {
+  size_t i = 0;
+  while (i < token.size()) {
+    const uint32_t c = next_cp(token, i);
+    if (c < 0x80 ? ((c >= '0' && c <= '9') || (c >= 'a' && c <= 'z') || (c >= 'A' && c <= 'Z'))
+                 : in_ranges(uni::kAlnum, c))
+      return true;
+  }
+  return false;
+}
+
+int32_t lex_row(const Tokenizer& tok, const std::string& text, int W, uint32_t* slots) {
+  std::vector<std::string> tokens;
+  tok.split_words(text, tokens);
+  std::vector<std::pair<uint32_t, uint32_t>> kept;  // (term, tf) in order of first appearance
+  kept.reserve((size_t)W);
+  int64_t dl = 0;
+  for (const auto& w : tokens) {
+    if (!lex_is_word(w)) continue;
+    ++dl;
+    const uint32_t t = lex_term_id(w);
+    bool found = false;
+    for (auto& e : kept)
+      if (e.first == t) { if (e.second < 255u) ++e.second; found = true; break; }
+    if (!found && (int)kept.size() < W) kept.emplace_back(t, 1u);
+    // (a term past the first W distinct ones is dropped; its words still count in dl)
+  }
+  std::sort(kept.begin(), kept.end());
+  for (int j = 0; j < W; ++j) slots[j] = j < (int)kept.size() ? ((kept[j].first << 8) | kept[j].second) : 0u;
+  return (int32_t)std::min<int64_t>(dl, 65535);
 }
 
 }  // namespace lzrt

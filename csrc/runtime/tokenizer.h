@@ -27,6 +27,8 @@ class Tokenizer {
   // overlapping max_len windows for texts longer than the model (owner = text index)
   int encode_chunks(const std::vector<std::string>& texts, int max_len, int overlap, std::vector<int32_t>& ids,
                     std::vector<int32_t>& lens, std::vector<int32_t>& owner) const;
+  // the basic split alone: the words the lexical terms are taken from
+  void split_words(const std::string& text, std::vector<std::string>& out) const { basic_split(text, out); }
 
  private:
   int vocab_size_;
@@ -36,5 +38,16 @@ class Tokenizer {
   void basic_split(const std::string& text, std::vector<std::string>& out) const;
   void wordpiece(const std::string& w, std::vector<int32_t>& out) const;
 };
+
+// Lexical terms of keyword search (lazzaro_amd/core/lexical.py holds the
+// definition; terms_py there is the same in Python). A word is a token of the
+// basic split with at least one alphanumeric code point; its term id is
+// t = (h ^ (h >> 24)) & 0xFFFFFF of h = FNV-1a 32 over its UTF-8 bytes, 0
+// mapped to 1. lex_row writes one text's row of W slots ((t << 8) | tf, the
+// first W distinct terms by appearance, ascending by t, zeros after) and
+// returns dl = the number of words, clipped at 65,535.
+uint32_t lex_term_id(const std::string& word);
+bool lex_is_word(const std::string& token);
+int32_t lex_row(const Tokenizer& tok, const std::string& text, int W, uint32_t* slots);
 
 }  // namespace lzrt

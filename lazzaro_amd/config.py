@@ -52,6 +52,7 @@ class MemoryConfig:
     ivf_min_rows: int = 1_000_000
     ivf_filtered: bool = False            # ivfpq: filtered searches scan the passing rows of the probed lists
     wide_k: bool = False                  # store searches with 16 < k <= 64 take the certified int8 route
+    lexical_slots: int = 16               # keyword search: term slots per memory in the lexicon (8, 16 or 32)
     hierarchy_mode: str = "reference"     # reference (one mean super-node per shard) | kmeans (two-level)
     hierarchy_fine: int = 4096            # kmeans: fine clusters
     hierarchy_top: int = 64               # kmeans: top-level clusters

@@ -1870,6 +1870,7 @@ class ConsolidationMixin:
                 continue
             r1, r2 = int(rows[i]), int(rows[j])
             g.content[r1] = f"{g.content[r1]} | {g.content[r2]}"
+            g._content_rewritten(r1)
             sal[r1] = max(sal[r1], sal[r2])
             acc[r1] = acc[r1] + acc[r2]
             g.set_scalar(r1, "sal", float(sal[r1]))

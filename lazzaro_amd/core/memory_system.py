@@ -234,7 +234,7 @@ class MemorySystem(ConsolidationMixin):
         kw.setdefault("index", cfg.index)
         kw.setdefault("index_params", {"nlist": cfg.nlist, "nprobe": cfg.nprobe, "pq_m": cfg.pq_m,
                                        "ivf_min_rows": cfg.ivf_min_rows, "ivf_filtered": cfg.ivf_filtered,
-                                       "wide_k": cfg.wide_k})
+                                       "wide_k": cfg.wide_k, "lexical_slots": cfg.lexical_slots})
         kw.setdefault("hierarchy_mode", cfg.hierarchy_mode)
         kw.setdefault("hierarchy_params", {"fine": cfg.hierarchy_fine, "top": cfg.hierarchy_top,
                                            "every": cfg.hierarchy_every})
@@ -345,9 +345,11 @@ class MemorySystem(ConsolidationMixin):
         fault_point("provider.llm")
         return self.llm.completion(messages, response_format)
 
-    def _search_batch(self, embs, k: int, where=None, mmr=None) -> List[List[str]]:
+    def _search_batch(self, embs, k: int, where=None, mmr=None, queries=None) -> List[List[str]]:
         if mmr is not None:  # (where= only when set, as below: the store sees the kwargs a caller gave)
             kw = dict(mmr) if where is None else dict(mmr, where=where)
+            if "lexical" in kw:
+                kw["query_texts"] = list(queries)
             return self.vector_store.search_nodes_batch(embs, user_id=self.user_id, limit=k, **kw)
         if where is not None:
             return self.vector_store.search_nodes_batch(embs, user_id=self.user_id, limit=k, where=where)
@@ -621,16 +623,28 @@ class MemorySystem(ConsolidationMixin):
             raise NotImplementedError("a filtered search (where=) needs a store bound to the tenant graph (HBMStore)")
         return flt
 
-    def _mmr(self, limit, diversity, fetch_k, expand=None, boost=None):
+    def _mmr(self, limit, diversity, fetch_k, expand=None, boost=None, lexical=None):
         """``diversity`` / ``fetch_k`` / ``expand`` / ``boost`` of a search as
         the kwargs the store is given (None: a plain search), validated before
         any work (both selections read the bound tenant graph's fp32 rows, the
         expansion its links, the boost its node columns; a store that holds
         its own rows has none of them). A boost's ``now`` is fixed here: once
-        per call."""
-        if diversity is None and fetch_k is None and expand is None and boost is None:
+        per call. ``lexical``: the settings of a keyword / hybrid search; the
+        queries' texts are added where the search is submitted."""
+        if diversity is None and fetch_k is None and expand is None and boost is None and lexical is None:
             return None
         kw = {}
+        if lexical is not None:
+            from .lexical import LexicalSearch
+            lexical = LexicalSearch.coerce(lexical)
+            if expand is not None or boost is not None:
+                raise NotImplementedError("lexical= does not compose with expand= or boost=")
+            if diversity is not None or fetch_k is not None:
+                from ..ops.mmr_ops import pool_size
+                lexical.check_limit(pool_size(limit, diversity, fetch_k))
+            else:
+                lexical.check_limit(limit)
+            kw.update(lexical=lexical)
         if boost is not None:
             from .boost import MemoryBoost
             kw.update(boost=MemoryBoost.coerce(boost).at())
@@ -646,13 +660,14 @@ class MemorySystem(ConsolidationMixin):
             kw.update(expand=expand)
         if not self._store_binds_graph():
             raise NotImplementedError(
-                ("a diverse search (diversity=)" if "diversity" in kw else "an expanded search (expand=)"
+                ("a lexical search (lexical=)" if "lexical" in kw else
+                 "a diverse search (diversity=)" if "diversity" in kw else "an expanded search (expand=)"
                  if "expand" in kw else "a boosted search (boost=)")
                 + " needs a store bound to the tenant graph (HBMStore)")
         return kw
 
     def search_memories(self, query: str, limit: int = 5, where=None, diversity=None, fetch_k=None,
-                        expand=None, boost=None) -> List[Node]:
+                        expand=None, boost=None, lexical=None) -> List[Node]:
         """``where`` (a :class:`MemoryFilter` or a dict of its fields): only
         the memories passing it are searched -- the ``limit`` nearest AMONG
         them, not a post-filter of the nearest. ``diversity`` (0 .. 1): the
@@ -666,10 +681,21 @@ class MemorySystem(ConsolidationMixin):
         activation their links carried (core/expand.py). ``boost`` (a number,
         a dict or a :class:`MemoryBoost`): the ``limit`` best by closeness
         PLUS a prior from each memory's salience, use and recency -- among
-        all memories, not a re-ordering of the nearest (core/boost.py)."""
+        all memories, not a re-ordering of the nearest (core/boost.py).
+        ``lexical`` (a number ``alpha`` in [0, 1], a dict or a
+        :class:`LexicalSearch`): keyword and hybrid search -- the ``limit``
+        best by ``(1 - alpha) * cosine + alpha * normalised BM25`` of the
+        query's words against each memory's content, over the union of the
+        ``pool`` nearest memories and the ``pool`` best keyword matches
+        (core/lexical.py); 1.0 is keyword search alone. Composes with
+        ``where`` and ``diversity``; not with ``expand`` or ``boost``."""
+        if lexical is not None and not isinstance(query, str):
+            raise ValueError("a lexical search needs the query's text")
         if where is not None:
             where = self._where(where)
-        mmr = self._mmr(limit, diversity, fetch_k, expand, boost)
+        mmr = self._mmr(limit, diversity, fetch_k, expand, boost, lexical)
+        if mmr is not None and "lexical" in mmr:
+            mmr = dict(mmr, query_text=query)
         with tracer.stage("embed_query", self._device):
             q = self._get_embedding(query)
         with self._graph_lock:
@@ -684,16 +710,16 @@ class MemorySystem(ConsolidationMixin):
             return [n for n in (self.buffer.get_node(i) for i in ids) if n is not None]
 
     def search_memories_batch(self, queries: List[str], limit: int = 5, where=None, diversity=None,
-                              fetch_k=None, expand=None, boost=None) -> List[List[Node]]:
+                              fetch_k=None, expand=None, boost=None, lexical=None) -> List[List[Node]]:
         """Batched ``search_memories`` (reference :1460-1472 per query): one
         embedding call (a device tensor when the encoder is on-device), one
         store search -- the fused MFMA candidate scan plus an fp32 re-rank
         over the tenant's HBM rows -- and one row -> Node mapping. ``where``,
-        ``diversity``, ``fetch_k``, ``expand``, ``boost``: one setting for the
-        whole batch (see :meth:`search_memories`)."""
+        ``diversity``, ``fetch_k``, ``expand``, ``boost``, ``lexical``: one
+        setting for the whole batch (see :meth:`search_memories`)."""
         if where is not None:
             where = self._where(where)
-        mmr = self._mmr(limit, diversity, fetch_k, expand, boost)
+        mmr = self._mmr(limit, diversity, fetch_k, expand, boost, lexical)
         t0 = time.perf_counter()
         out = self._search_finish(self._search_submit(queries, limit, where, mmr))
         self._count_search(len(out), (time.perf_counter() - t0) * 1e3)
@@ -706,18 +732,18 @@ class MemorySystem(ConsolidationMixin):
         m["search_ms"] = m.get("search_ms", 0.0) + ms
 
     def search_memories_stream(self, batches: Iterable[List[str]], limit: int = 5, where=None, diversity=None,
-                               fetch_k=None, expand=None, boost=None):
+                               fetch_k=None, expand=None, boost=None, lexical=None):
         """Pipelined ``search_memories_batch`` for serving loops: batches i+1 ..
         i+STREAM_DEPTH are tokenised and their embed + scan enqueued on the
         device BEFORE the host waits for batch i and maps its rows to Nodes,
         so host work (tokenizer, result mapping) hides under device work.
         Yields one result list per input batch, in order; results equal
         ``search_memories_batch``. ``where``, ``diversity``, ``fetch_k``,
-        ``expand``, ``boost``: one setting for all batches (a boost's ``now``
-        is read once, for the whole stream)."""
+        ``expand``, ``boost``, ``lexical``: one setting for all batches (a
+        boost's ``now`` is read once, for the whole stream)."""
         if where is not None:
             where = self._where(where)
-        mmr = self._mmr(limit, diversity, fetch_k, expand, boost)
+        mmr = self._mmr(limit, diversity, fetch_k, expand, boost, lexical)
         pending = collections.deque()
         for qs in batches:
             pending.append(self._search_submit(qs, limit, where, mmr))
@@ -729,8 +755,18 @@ class MemorySystem(ConsolidationMixin):
     def _search_submit(self, queries, limit: int, where=None, mmr=None):
         """Enqueue embed + store search; returns a handle for _search_finish.
         With the graph-bound store the result rows stay on the device and come
-        back with one async copy into pinned memory (no host sync here)."""
+        back with one async copy into pinned memory (no host sync here; a
+        lexical search uploads its term tables from pageable memory, a copy the
+        host waits for)."""
         queries = list(queries)
+        lex = mmr is not None and "lexical" in mmr
+        if lex:  # the queries' terms, on the host
+            from .lexical import as_query_terms
+            if not all(isinstance(q, str) for q in queries):
+                raise ValueError("a lexical search needs the queries' text")
+            gmmr = dict(mmr, query_terms=as_query_terms(queries)) if queries else mmr
+        else:
+            gmmr = mmr
         with tracer.stage("embed_query", self._device):
             embs = self._batch_embed_any(queries)
         with self._graph_lock:
@@ -755,7 +791,7 @@ class MemorySystem(ConsolidationMixin):
                         # mapping needs no mirror
                         if mmr is not None:  # (the pool search marks non-node rows: they take no pick)
                             _, rows = g.store_search(embs, int(limit), getattr(self.store, "metric", "l2"),
-                                                     node_rows=True, where=where, **mmr)
+                                                     node_rows=True, where=where, **gmmr)
                         elif where is None:
                             _, rows = g.store_search(embs, int(limit), getattr(self.store, "metric", "l2"),
                                                      node_rows=True)
@@ -772,7 +808,7 @@ class MemorySystem(ConsolidationMixin):
                         return ("rows_dev", g, rows, ev, g.row_epoch)
                     return ("rows", g, rows, None, g.row_epoch)
         with tracer.stage("search", self._device):
-            return ("ids", None, self._search_batch(embs, limit, where, mmr), None, 0)
+            return ("ids", None, self._search_batch(embs, limit, where, mmr, queries), None, 0)
 
     def _search_finish(self, h) -> List[List[Node]]:
         kind_, g0, data, ev, epoch = h  # (the row epoch searched under: a compaction may run before the finish)
@@ -850,6 +886,9 @@ class MemorySystem(ConsolidationMixin):
                 "filtered_sparse": g.filtered_sparse, "filtered_ann": g.filtered_ann,
                 "mmr_searches": g.mmr_searches, "expanded_searches": g.expanded_searches,
                 "boosted_searches": g.boosted_searches, "boost_columns_built": g.boost_columns_built,
+                "lexical_searches": g.lexical_searches,
+                "lexicon_rows": 0 if g._lexicon is None else g._lexicon.covered,
+                "lexicon_builds": 0 if g._lexicon is None else g._lexicon.builds,
                 "wide_searches": g.wide_searches, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,
                 "avg_search_batch_ms": round(sms / m["search_batches"], 3) if m.get("search_batches") else 0.0}
 

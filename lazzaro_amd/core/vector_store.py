@@ -55,16 +55,21 @@ class HBMStore:
     def __init__(self, db_dir: str = "db", device=None, metric: str = "l2",
                  consistency_interval: float = 0.5, keep_fp32: bool = True, index: str = "flat",
                  nlist: int = 4096, nprobe: int = 32, pq_m: int = 64, ivf_min_rows: int = 1_000_000,
-                 ivf_filtered: bool = False, wide_k: bool = False):
+                 ivf_filtered: bool = False, wide_k: bool = False, lexical_slots: int = 16):
         """index="ivfpq": a tenant arena with >= ivf_min_rows live rows is served
         by IVF-PQ candidates re-ranked exactly (smaller tenants stay exact flat).
         ivf_filtered: an attached tenant graph's filtered searches (``where=``)
         may use the index too, scanning only the passing rows of the probed
         lists (TenantGraph._store_search_where); off: they take the flat routes.
         wide_k: an attached tenant graph serves searches with 16 < k <= 64 on the
-        certified int8 candidate route (TenantGraph.wide_k); off: the exact fp32 scan."""
+        certified int8 candidate route (TenantGraph.wide_k); off: the exact fp32 scan.
+        lexical_slots: the term slots per memory of an attached graph's lexicon
+        (keyword search, ``lexical=``): 8, 16 or 32."""
         if index not in ("flat", "ivfpq"):
             raise ValueError("index must be 'flat' or 'ivfpq'")
+        if int(lexical_slots) not in (8, 16, 32):
+            raise ValueError(f"lexical_slots must be 8, 16 or 32 (got {lexical_slots})")
+        self.lexical_slots = int(lexical_slots)
         self.index, self.ivf_params = index, dict(nlist=nlist, nprobe=nprobe, m=pq_m, min_rows=ivf_min_rows)
         self.ivf_filtered = bool(ivf_filtered)
         self.wide_k = bool(wide_k)
@@ -95,6 +100,8 @@ class HBMStore:
             self._synced.pop(user_id, None)
             if self.wide_k:
                 graph.wide_k = True
+            if self.lexical_slots != 16:
+                graph.lexical_slots = self.lexical_slots
             if self.index == "ivfpq":  # large tenants: IVF-PQ candidates + exact fp32 re-rank on the graph
                 graph.ann_cfg = dict(self.ivf_params, filtered=self.ivf_filtered)
 
@@ -284,12 +291,16 @@ class HBMStore:
         raise NotImplementedError(
             f"an expanded search (expand=) needs the tenant's graph attached to the store; {user_id!r} has none")
 
+    def _lexical_needs_graph(self, user_id: str):
+        raise NotImplementedError(
+            f"a lexical search (lexical=) needs the tenant's graph attached to the store; {user_id!r} has none")
+
     def _boost_needs_graph(self, user_id: str):
         raise NotImplementedError(
             f"a boosted search (boost=) needs the tenant's graph attached to the store; {user_id!r} has none")
 
     def search_nodes(self, query_emb, user_id: str = "default", limit: int = 5, where=None, diversity=None,
-                     fetch_k=None, expand=None, boost=None) -> List[str]:
+                     fetch_k=None, expand=None, boost=None, lexical=None, query_text=None) -> List[str]:
         """``where`` (a MemoryFilter or a dict of its fields): only the
         tenant's memories passing it are searched (core/filters.py).
         ``diversity`` / ``fetch_k``: the results are picked from the
@@ -297,10 +308,21 @@ class HBMStore:
         (TenantGraph.store_search). ``expand``: the links of the nearest are
         followed and the best of everything reached come back
         (core/expand.py). ``boost``: the best by closeness plus a prior from
-        salience, use and recency (core/boost.py)."""
+        salience, use and recency (core/boost.py). ``lexical`` with
+        ``query_text`` (the query's text): keyword and hybrid search
+        (core/lexical.py)."""
+        if lexical is not None:
+            from .lexical import LexicalSearch
+            lexical = LexicalSearch.coerce(lexical)
+            if expand is not None or boost is not None:
+                raise NotImplementedError("lexical= does not compose with expand= or boost=")
+            if not isinstance(query_text, str):
+                raise ValueError("a lexical search needs the query's text: pass query_text=")
         if query_emb is None or len(query_emb) == 0:
             return []
         g = self._graphs.get(user_id)
+        if lexical is not None and g is None:
+            self._lexical_needs_graph(user_id)
         if where is not None and g is None:
             self._filter_needs_graph(user_id)
         mmr = diversity is not None or fetch_k is not None
@@ -316,6 +338,9 @@ class HBMStore:
             with g.lock:  # the tenant's graph lock: a consolidation may be writing
                 if g.dim is None or q.shape[-1] != g.dim:
                     return []
+                if lexical is not None:
+                    return g.search_ids(q, int(limit), self.metric, where, diversity, fetch_k, lexical=lexical,
+                                        query_terms=[query_text])[0]
                 if mmr or expand is not None or boost is not None:
                     return g.search_ids(q, int(limit), self.metric, where, diversity, fetch_k, expand, boost)[0]
                 return g.search_ids(q, int(limit), self.metric, where)[0]
@@ -326,12 +351,24 @@ class HBMStore:
             return a.search(query_emb, int(limit), self.metric)[0]
 
     def search_nodes_batch(self, query_embs, user_id: str = "default", limit: int = 5,
-                           where=None, diversity=None, fetch_k=None, expand=None, boost=None) -> List[List[str]]:
+                           where=None, diversity=None, fetch_k=None, expand=None, boost=None, lexical=None,
+                           query_texts=None) -> List[List[str]]:
         """Batched variant (one kernel launch for all queries). ``query_embs``
         may be a device tensor (kept on the device end to end). ``where``,
         ``diversity``, ``fetch_k``, ``expand``, ``boost``: one setting for the
-        whole batch (see :meth:`search_nodes`)."""
+        whole batch (see :meth:`search_nodes`). ``lexical`` with
+        ``query_texts``: the queries' texts, one per embedding."""
+        if lexical is not None:
+            from .lexical import LexicalSearch
+            lexical = LexicalSearch.coerce(lexical)
+            if expand is not None or boost is not None:
+                raise NotImplementedError("lexical= does not compose with expand= or boost=")
+            if query_texts is None or isinstance(query_texts, str) or len(query_texts) != len(query_embs) \
+                    or not all(isinstance(t, str) for t in query_texts):
+                raise ValueError("a lexical search needs the queries' texts, one per query: pass query_texts=")
         g = self._graphs.get(user_id)
+        if lexical is not None and g is None:
+            self._lexical_needs_graph(user_id)
         if where is not None and g is None:
             self._filter_needs_graph(user_id)
         mmr = diversity is not None or fetch_k is not None
@@ -349,6 +386,9 @@ class HBMStore:
             with g.lock:
                 if g.dim is None or Q.shape[-1] != g.dim:
                     return [[] for _ in range(len(Q))]
+                if lexical is not None:
+                    return g.search_ids(Q, int(limit), self.metric, where, diversity, fetch_k, lexical=lexical,
+                                        query_terms=list(query_texts))
                 if mmr or expand is not None or boost is not None:
                     return g.search_ids(Q, int(limit), self.metric, where, diversity, fetch_k, expand, boost)
                 return g.search_ids(Q, int(limit), self.metric, where)
@@ -359,7 +399,7 @@ class HBMStore:
             return a.search(query_embs, int(limit), self.metric)
 
     def search_nodes_multi(self, query_embs, user_ids: Sequence[str], limit: int = 5, where=None, diversity=None,
-                           fetch_k=None, expand=None, boost=None) -> List[List[str]]:
+                           fetch_k=None, expand=None, boost=None, lexical=None) -> List[List[str]]:
         """Multi-tenant batch: query i searches tenant ``user_ids[i]`` only, all
         in one kernel launch (serving many users per GPU, BASELINE config 3).
         Filters, diverse selection, graph expansion and boosts are not
@@ -376,6 +416,9 @@ class HBMStore:
                                       "expand=")
         if boost is not None:
             raise NotImplementedError("search_nodes_multi does not boost; search each tenant with boost=")
+        if lexical is not None:
+            raise NotImplementedError("search_nodes_multi does not search by keyword; search each tenant with "
+                                      "lexical=")
         if len(user_ids) == 0:
             return []
         with self._lock:

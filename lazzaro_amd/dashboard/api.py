@@ -108,7 +108,8 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
                  super_nodes: Optional[bool] = None, exclude_ids: Optional[str] = None,
                  diversity: Optional[float] = None, fetch_k: Optional[int] = None,
                  hops: Optional[int] = None, fanout: Optional[int] = None, graph_weight: Optional[float] = None,
-                 boost: Optional[float] = None, boost_recency_scale: Optional[float] = None):
+                 boost: Optional[float] = None, boost_recency_scale: Optional[float] = None,
+                 lexical: Optional[float] = None, lexical_pool: Optional[int] = None):
     """``MemoryFilter`` fields as optional query parameters (the set-valued
     ones comma separated); none given: the unfiltered search. ``diversity``
     (0 .. 1) and ``fetch_k``: results picked for diversity from the
@@ -119,7 +120,10 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
     by closeness plus ``w`` times each memory's importance -- salience 0.5 w,
     use 0.3 w, recency 0.2 w (``boost=``, core/boost.py);
     ``boost_recency_scale``: the recency term's scale in seconds (default one
-    day; given alone it changes nothing)."""
+    day; given alone it changes nothing). ``lexical`` (``alpha`` in 0 .. 1):
+    keyword and hybrid search over the memories' words (``lexical=``,
+    core/lexical.py); ``lexical_pool``: its candidate pool (default 16; given
+    alone it changes nothing)."""
     if not _ms:
         return []
     where = {k: v for k, v in (("types", _csv(types)), ("shard_keys", _csv(shard_keys)),
@@ -139,6 +143,11 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
         if boost_recency_scale is not None:
             b["recency_scale"] = boost_recency_scale
         kw.update(boost=b)
+    if lexical is not None:
+        lx = {"alpha": lexical}
+        if lexical_pool is not None:
+            lx["pool"] = lexical_pool
+        kw.update(lexical=lx)
     hits = _ms.search_memories(q, limit=limit, **kw)
     return [{"id": n.id, "content": n.content, "salience": n.salience, "shard": n.shard_key} for n in hits]
 

@@ -745,6 +745,7 @@ class TenantGraph:
                     if kind_h is not None and r < len(kind_h) and kind_h[r] == NODE:
                         self._unlink_row(r)
                     self.content[r] = contents[j]
+                    self._content_rewritten(r)
                     if self.types[r] != t:
                         self._type_rewritten(r)
                     self.types[r] = t
@@ -2460,7 +2461,8 @@ class TenantGraph:
         return b
 
     def store_search(self, Q: torch.Tensor, k: int, metric: str = "l2", node_rows: bool = False, where=None,
-                     diversity: Optional[float] = None, fetch_k: Optional[int] = None, expand=None, boost=None):
+                     diversity: Optional[float] = None, fetch_k: Optional[int] = None, expand=None, boost=None,
+                     lexical=None, query_terms=None):
         """The store's vector search over this tenant (reference
         ``LanceDBStore.search_nodes``: flat scan, L2 unless told otherwise,
         vector_store.py:132-140). fp32 scores -- -|q-x|^2 for L2, cosine, or
@@ -2483,7 +2485,25 @@ class TenantGraph:
         ``k`` rows with the largest ``score + prior`` among the graph nodes in
         the store, the prior built from salience, use and recency
         (:meth:`boost_bias`); the scores returned include it. With
-        ``diversity`` / ``expand`` it decides their pool / seeds only."""
+        ``diversity`` / ``expand`` it decides their pool / seeds only.
+        ``lexical`` (a number ``alpha``, a dict or a
+        ``core.lexical.LexicalSearch``) with ``query_terms`` (the queries'
+        texts, or their term ids [M, T <= 32]): keyword and hybrid search
+        (:meth:`_store_search_lex`) -- the ``k`` best by ``(1 - alpha) * cos +
+        alpha * normalised BM25`` over the union of the nearest and the best
+        keyword matches; memories only. With ``diversity`` it is the pool
+        search; with ``expand`` or ``boost`` it raises."""
+        if lexical is not None:
+            from ..core.lexical import LexicalSearch
+            lexical = LexicalSearch.coerce(lexical)
+            if expand is not None or boost is not None:
+                raise NotImplementedError("lexical= does not compose with expand= or boost=")
+            if query_terms is None:
+                raise ValueError("a lexical search needs the queries' text: pass query_terms=")
+            if diversity is not None or fetch_k is not None:
+                return self._store_search_mmr(Q, k, metric, node_rows, where, diversity, fetch_k, lexical=lexical,
+                                              query_terms=query_terms)
+            return self._store_search_lex(Q, k, metric, where, lexical, query_terms)
         if boost is not None:
             from ..core.boost import MemoryBoost
             boost = MemoryBoost.coerce(boost).at()  # (``now`` is read once, here)
@@ -2515,13 +2535,15 @@ class TenantGraph:
 
     mmr_searches = 0
 
-    def _store_search_mmr(self, Q, k, metric, node_rows, where, diversity, fetch_k, expand=None, boost=None):
+    def _store_search_mmr(self, Q, k, metric, node_rows, where, diversity, fetch_k, expand=None, boost=None,
+                          lexical=None, query_terms=None):
         """:meth:`store_search` with ``diversity``: the pool is the plain
         search at ``k = fetch_k`` (default ``max(16, 2 k)``, at most
         MAX_FETCH_K = 64) by whatever route that takes, ``node_rows`` and
         ``where`` passed through (with ``expand``, the expanded search at
         ``k = fetch_k`` and its blended scores; with ``boost``, the boosted
-        search at ``k = fetch_k`` and its boosted scores); rows it marked -1 are not
+        search at ``k = fetch_k`` and its boosted scores; with ``lexical``,
+        the fused search at ``k = fetch_k`` and its blends); rows it marked -1 are not
         candidates. The ``k`` picks are greedy maximal marginal relevance
         over the pool's fp32 rows (ops.mmr_ops.mmr_select: cosine relevance
         and cosine redundancy whatever the metric, ties to the lower row),
@@ -2530,7 +2552,10 @@ class TenantGraph:
         from ..ops.mmr_ops import mmr_select, pool_size
         k = int(k)
         F = pool_size(k, diversity, fetch_k)
-        s, r = self.store_search(Q, F, metric, node_rows, where, expand=expand, boost=boost)
+        if lexical is not None:
+            s, r = self.store_search(Q, F, metric, node_rows, where, lexical=lexical, query_terms=query_terms)
+        else:
+            s, r = self.store_search(Q, F, metric, node_rows, where, expand=expand, boost=boost)
         self.mmr_searches += 1
         with self.on_stream():
             Qf = Q.to(self.device, torch.float32)
@@ -2590,6 +2615,100 @@ class TenantGraph:
             rows, scores, via, _ = expand_select(self.emb32[:n], Qf, seeds, csr, self.e["w"], self.kind, self.sup,
                                                  bias, sp, k)
         return scores, rows, via
+
+    # ---- keyword and hybrid search
+    _lexicon = None  # the derived lexical index (engine/lexicon.py), built on the first lexical search
+    lexical_slots = 16  # W: term slots per row (MemoryConfig.lexical_slots)
+    lexical_searches = 0
+
+    def _content_rewritten(self, r: int) -> None:
+        """The content of row ``r`` changed: its terms are taken again at the
+        next lexical search."""
+        if self._lexicon is not None:
+            self._lexicon.rewritten(r)
+
+    def lexicon(self):
+        """The tenant's lexicon, synced to rows [0, n) (built on first use)."""
+        from .lexicon import Lexicon
+        if self._lexicon is None or self._lexicon.W != int(self.lexical_slots):
+            builds = 0 if self._lexicon is None else self._lexicon.builds
+            self._lexicon = Lexicon(self, self.lexical_slots)
+            self._lexicon.builds = builds
+        with self.on_stream():
+            return self._lexicon.sync()
+
+    def _lex_bias(self, metric: str, where):
+        """The eligibility column of a lexical search: the filter plan's bias
+        (finite where the row is a memory in the store that passes ``where``)."""
+        from ..core.filters import MemoryFilter
+        flt = MemoryFilter.coerce(where) if where is not None else MemoryFilter()
+        return self._filter_plan(flt, metric == "l2").bias
+
+    def lexical_topk(self, texts_or_terms, k: int, where=None, k1: float = 1.2, b: float = 0.75,
+                     metric: str = "l2"):
+        """The lexical leg alone: per query the ``k`` (<= 64) memories passing
+        ``where`` with the largest BM25 score (ops/lex_ops.py), (scores [M, k],
+        rows [M, k]), descending, ties to the lower row, (-inf, -1) padded."""
+        from ..ops.lex_ops import NEG_INF as _NI, _check_params, lex_topk
+        from ..core.lexical import as_query_terms
+        k = int(k)
+        _check_params(k, k1, b, 1.0)
+        qt = as_query_terms(texts_or_terms)
+        M = qt.shape[0]
+        if self.n == 0:
+            return (torch.full((M, k), _NI, device=self.device),
+                    torch.full((M, k), -1, dtype=torch.long, device=self.device))
+        with self.on_stream():
+            self.lexical_searches += 1
+            lx = self.lexicon()
+            n = self.n
+            return lex_topk(lx.slots[:n], lx.dl[:n], self._lex_bias(metric, where), qt, lx.weights(qt), k, k1, b,
+                            lx.avgdl)
+
+    def _store_search_lex(self, Q, k, metric, where, lexical, query_terms):
+        """:meth:`store_search` with ``lexical``. Candidates: the dense pool
+        -- the plain search at ``k = pool`` with ``node_rows=True`` and
+        ``where`` passed through, by whatever route that takes (skipped at
+        ``alpha = 1``) -- and the lexical pool, the ``pool`` best memories by
+        BM25 among those passing ``where``. Every candidate scores ``(1 -
+        alpha) * cos + alpha * lexn`` over the fp32 rows whatever the metric
+        (ops.lex_ops.lex_fuse), BM25 recomputed for each; the ``k`` best come
+        back, descending, ties to the lower row, (-inf, -1) once the
+        candidates run out. Building or extending the lexicon is host work;
+        a search over a synced lexicon reads nothing back from the device
+        beyond the filter plan's count, but uploads the queries' term tables
+        and weights from pageable host memory (ops/lex_ops.py), which the
+        host waits for."""
+        from ..core.lexical import as_query_terms
+        from ..ops.lex_ops import lex_fuse, lex_topk
+        k = int(k)
+        lexical.check_limit(k)
+        dev = self.device
+        Qf = Q.to(dev, torch.float32)
+        if Qf.dim() == 1:
+            Qf = Qf[None, :]
+        M = Qf.shape[0]
+        qt = as_query_terms(query_terms)
+        if qt.shape[0] != M:
+            raise ValueError(f"{M} queries but the terms of {qt.shape[0]}")
+        n = self.n
+        if n == 0 or self.dim is None or Qf.shape[1] != self.dim:  # (nothing to search: all padding)
+            return (torch.full((M, k), NEG_INF, device=dev), torch.full((M, k), -1, dtype=torch.long, device=dev))
+        if self.emb32 is None:
+            raise NotImplementedError("a lexical search needs the tenant's fp32 rows")
+        P = lexical.pool
+        dense = None
+        if lexical.alpha < 1.0:
+            _, dense = self.store_search(Q, P, metric, True, where)
+        with self.on_stream():
+            self.lexical_searches += 1
+            lx = self.lexicon()
+            w = lx.weights(qt)
+            avgdl = lx.avgdl
+            _, lp = lex_topk(lx.slots[:n], lx.dl[:n], self._lex_bias(metric, where), qt, w, P, lexical.k1, lexical.b,
+                             avgdl)
+            return lex_fuse(self.emb32[:n], Qf, dense, lp, lx.slots, lx.dl, qt, w, lexical.alpha, k, lexical.k1,
+                            lexical.b, avgdl)
 
     # ---- boosted search
     _boost_cols = None  # OrderedDict: column key -> FilterPlan holding the boosted column (LRU, BOOST_COLUMN_CACHE)
@@ -3108,8 +3227,11 @@ class TenantGraph:
         return self._pad_k(torch.gather(s, 1, o), torch.gather(cand, 1, o), k)
 
     def search_ids(self, Q, k: int, metric: str = "l2", where=None, diversity=None, fetch_k=None,
-                   expand=None, boost=None) -> List[List[str]]:
-        if diversity is not None or fetch_k is not None or expand is not None or boost is not None:
+                   expand=None, boost=None, lexical=None, query_terms=None) -> List[List[str]]:
+        if lexical is not None:
+            _, r = self.store_search(Q, k, metric, node_rows=True, where=where, diversity=diversity, fetch_k=fetch_k,
+                                     expand=expand, boost=boost, lexical=lexical, query_terms=query_terms)
+        elif diversity is not None or fetch_k is not None or expand is not None or boost is not None:
             # (node rows only: a row the caller would drop must not take a pick)
             _, r = self.store_search(Q, k, metric, node_rows=True, where=where, diversity=diversity, fetch_k=fetch_k,
                                      expand=expand, boost=boost)

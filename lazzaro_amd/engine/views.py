@@ -116,6 +116,7 @@ class NodeView(Node):
     @content.setter
     def content(self, v: str) -> None:
         self._g.content[self._r] = v
+        self._g._content_rewritten(self._r)
         self._g.set_scalar(self._r, "dirty", 1)
 
     @property

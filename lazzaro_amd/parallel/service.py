@@ -693,7 +693,9 @@ class DistributedMemoryService:
 
     # ------------------------------------------------------------ columnar search (routing.py)
     @staticmethod
-    def _no_mmr(what: str, diversity, fetch_k, expand=None, boost=None) -> None:
+    def _no_mmr(what: str, diversity, fetch_k, expand=None, boost=None, lexical=None) -> None:
+        if lexical is not None:
+            raise NotImplementedError(f"DistributedMemoryService.{what} does not search by keyword (lexical=)")
         if diversity is not None or fetch_k is not None:
             raise NotImplementedError(f"DistributedMemoryService.{what} does not select by diversity (diversity=)")
         if expand is not None:
@@ -702,7 +704,7 @@ class DistributedMemoryService:
             raise NotImplementedError(f"DistributedMemoryService.{what} does not boost (boost=)")
 
     def search_routed(self, users: Sequence[str], queries, limit=5, where=None, diversity=None,
-                      fetch_k=None, expand=None, boost=None) -> "routing.RoutedHits":
+                      fetch_k=None, expand=None, boost=None, lexical=None) -> "routing.RoutedHits":
         """SPMD batched search_memories with tensors on the wire: ``queries``
         are texts (embedded here, by this rank's replica of the encoder) or an
         embedding tensor [n, D]; each goes to ``users[q]``'s owner in one
@@ -710,12 +712,12 @@ class DistributedMemoryService:
         :class:`~.routing.RoutedHits` in the caller's order."""
         if where is not None:
             raise NotImplementedError("DistributedMemoryService.search_routed takes no filter (where=)")
-        DistributedMemoryService._no_mmr("search_routed", diversity, fetch_k, expand, boost)
+        DistributedMemoryService._no_mmr("search_routed", diversity, fetch_k, expand, boost, lexical)
         Q = self._embed_front(queries)
         return routing.search_routed(self, list(users), Q, limit)
 
     def search_routed_stream(self, batches, limit=5, where=None, diversity=None, fetch_k=None, expand=None,
-                             boost=None):
+                             boost=None, lexical=None):
         """Pipelined :meth:`search_routed` for serving loops (the routed
         counterpart of ``MemorySystem.search_memories_stream``): ``batches``
         yields (users, query texts); batch i+1's front-end embed is enqueued
@@ -725,7 +727,7 @@ class DistributedMemoryService:
         Yields one :class:`~.routing.RoutedHits` per batch, in order."""
         if where is not None:
             raise NotImplementedError("DistributedMemoryService.search_routed_stream takes no filter (where=)")
-        DistributedMemoryService._no_mmr("search_routed_stream", diversity, fetch_k, expand, boost)
+        DistributedMemoryService._no_mmr("search_routed_stream", diversity, fetch_k, expand, boost, lexical)
         dev = self.comm.device
         side = None
         if dev.type == "cuda":
@@ -758,12 +760,12 @@ class DistributedMemoryService:
             cur, q_cur = nxt, q_nxt
 
     def search_global_batch(self, queries, limit: int = 5, where=None, diversity=None,
-                            fetch_k=None, expand=None, boost=None) -> "routing.GlobalHits":
+                            fetch_k=None, expand=None, boost=None, lexical=None) -> "routing.GlobalHits":
         """SPMD: this rank's queries against every resident tenant of every
         rank (all-gather of queries, local search, one all-to-all back)."""
         if where is not None:
             raise NotImplementedError("DistributedMemoryService.search_global_batch takes no filter (where=)")
-        DistributedMemoryService._no_mmr("search_global_batch", diversity, fetch_k, expand, boost)
+        DistributedMemoryService._no_mmr("search_global_batch", diversity, fetch_k, expand, boost, lexical)
         return routing.search_global_batch(self, self._embed_front(queries), limit)
 
     def resolve(self, hits: "routing.RoutedHits") -> List[List[Dict]]:
@@ -802,13 +804,13 @@ class DistributedMemoryService:
 
     # ------------------------------------------------------------ global search (C1 + K2)
     def search_global(self, query_emb: torch.Tensor, limit: int = 5, metric: str = "l2", where=None, diversity=None,
-                      fetch_k=None, expand=None, boost=None) -> List[Dict]:
+                      fetch_k=None, expand=None, boost=None, lexical=None) -> List[Dict]:
         """Top-``limit`` over every resident tenant of every rank for one
         query vector (exact store scores: -|q-x|^2 for L2). Returns the same
         list of {user_id, node...} dicts on every rank."""
         if where is not None:
             raise NotImplementedError("DistributedMemoryService.search_global takes no filter (where=)")
-        DistributedMemoryService._no_mmr("search_global", diversity, fetch_k, expand, boost)
+        DistributedMemoryService._no_mmr("search_global", diversity, fetch_k, expand, boost, lexical)
         comm = self.comm
         cands = []
         for user, ms in self.systems.items():

@@ -573,7 +573,7 @@ class ShardedMemorySystem:
         return out
 
     def search_memories_batch(self, queries: Sequence[str], limit: int = 5, where=None, diversity=None,
-                              fetch_k=None, expand=None, boost=None) -> List[List[Dict]]:
+                              fetch_k=None, expand=None, boost=None, lexical=None) -> List[List[Dict]]:
         """Collective ``search_memories`` over the whole tenant (reference
         :1460-1472): every rank embeds its own queries, the query rows are
         all-gathered, each rank runs the store search (fused scan + fp32
@@ -588,6 +588,8 @@ class ShardedMemorySystem:
             raise NotImplementedError("ShardedMemorySystem.search_memories_batch does not expand along links (expand=)")
         if boost is not None:
             raise NotImplementedError("ShardedMemorySystem.search_memories_batch does not boost (boost=)")
+        if lexical is not None:
+            raise NotImplementedError("ShardedMemorySystem.search_memories_batch does not search by keyword (lexical=)")
 
         g = self.g
         dev = self.device
