@@ -48,12 +48,12 @@ from ..engine.views import GraphBuffer, NodeView, ResultBatch, ShardView, Shards
 from ..models.graph import Edge, Node
 from . import providers as _providers
 from .consolidation import ConsolidationMixin
-from .filters import MemoryFilter
 from .interfaces import EmbeddingProvider, LLMProvider, Store
 from .memory_shard import MemoryShard
 from .profile import EMPTY_CONTEXT, Profile
 from .providers import HashEmbedder, LocalLLM, OpenAIEmbedder, OpenAILLM, cosine
 from .query_cache import QueryCache
+from .search_spec import SearchSpec
 from .vector_store import HBMStore
 from ..utils.faults import StoreError, degenerate_embedding, fault_point
 from ..utils.tracing import tracer
@@ -345,14 +345,10 @@ class MemorySystem(ConsolidationMixin):
         fault_point("provider.llm")
         return self.llm.completion(messages, response_format)
 
-    def _search_batch(self, embs, k: int, where=None, mmr=None, queries=None) -> List[List[str]]:
-        if mmr is not None:  # (where= only when set, as below: the store sees the kwargs a caller gave)
-            kw = dict(mmr) if where is None else dict(mmr, where=where)
-            if "lexical" in kw:
-                kw["query_texts"] = list(queries)
-            return self.vector_store.search_nodes_batch(embs, user_id=self.user_id, limit=k, **kw)
-        if where is not None:
-            return self.vector_store.search_nodes_batch(embs, user_id=self.user_id, limit=k, where=where)
+    def _search_batch(self, embs, k: int, spec=None, queries=None) -> List[List[str]]:
+        if spec is not None:  # (the store sees the options a caller gave, and nothing else)
+            return self.vector_store.search_nodes_batch(embs, user_id=self.user_id, limit=k,
+                                                        **spec.kwargs(query_texts=list(queries)))
         fn = getattr(self.vector_store, "search_nodes_batch", None)
         if fn is not None:
             return fn(embs, user_id=self.user_id, limit=k)
@@ -615,56 +611,15 @@ class MemorySystem(ConsolidationMixin):
         kind = g.flags_of(out)[0]
         return [NodeView.of(g, x) for x, k in zip(out, kind) if k == NODE]
 
-    def _where(self, where):
-        """``where`` of a search as a MemoryFilter (the predicate runs over the
-        bound tenant graph's HBM columns; a store that holds its own rows has none)."""
-        flt = MemoryFilter.coerce(where)
-        if flt is not None and not self._store_binds_graph():
-            raise NotImplementedError("a filtered search (where=) needs a store bound to the tenant graph (HBMStore)")
-        return flt
-
-    def _mmr(self, limit, diversity, fetch_k, expand=None, boost=None, lexical=None):
-        """``diversity`` / ``fetch_k`` / ``expand`` / ``boost`` of a search as
-        the kwargs the store is given (None: a plain search), validated before
-        any work (both selections read the bound tenant graph's fp32 rows, the
-        expansion its links, the boost its node columns; a store that holds
-        its own rows has none of them). A boost's ``now`` is fixed here: once
-        per call. ``lexical``: the settings of a keyword / hybrid search; the
-        queries' texts are added where the search is submitted."""
-        if diversity is None and fetch_k is None and expand is None and boost is None and lexical is None:
-            return None
-        kw = {}
-        if lexical is not None:
-            from .lexical import LexicalSearch
-            lexical = LexicalSearch.coerce(lexical)
-            if expand is not None or boost is not None:
-                raise NotImplementedError("lexical= does not compose with expand= or boost=")
-            if diversity is not None or fetch_k is not None:
-                from ..ops.mmr_ops import pool_size
-                lexical.check_limit(pool_size(limit, diversity, fetch_k))
-            else:
-                lexical.check_limit(limit)
-            kw.update(lexical=lexical)
-        if boost is not None:
-            from .boost import MemoryBoost
-            kw.update(boost=MemoryBoost.coerce(boost).at())
-        if diversity is not None or fetch_k is not None:
-            from ..ops.mmr_ops import pool_size
-            pool_size(limit, diversity, fetch_k)
-            kw.update(diversity=float(diversity), fetch_k=fetch_k)
-        if expand is not None:
-            from ..ops.expand_ops import pool_bound
-            from .expand import GraphExpand
-            expand = GraphExpand.coerce(expand)
-            pool_bound(expand, limit if not kw else None)  # (with diversity= the expansion returns the pool)
-            kw.update(expand=expand)
-        if not self._store_binds_graph():
-            raise NotImplementedError(
-                ("a lexical search (lexical=)" if "lexical" in kw else
-                 "a diverse search (diversity=)" if "diversity" in kw else "an expanded search (expand=)"
-                 if "expand" in kw else "a boosted search (boost=)")
-                + " needs a store bound to the tenant graph (HBMStore)")
-        return kw
+    def _spec(self, limit, where, diversity, fetch_k, expand, boost, lexical):
+        """The options of a search as a :class:`SearchSpec` (None: a plain
+        search), validated before any work. Every option reads the bound
+        tenant graph -- its HBM columns, fp32 rows, links or contents; a store
+        that holds its own rows has none of them."""
+        spec = SearchSpec.of(limit, where, diversity, fetch_k, expand, boost, lexical)
+        if spec is not None and not self._store_binds_graph():
+            spec.needs("a store bound to the tenant graph (HBMStore)")
+        return spec
 
     def search_memories(self, query: str, limit: int = 5, where=None, diversity=None, fetch_k=None,
                         expand=None, boost=None, lexical=None) -> List[Node]:
@@ -691,22 +646,13 @@ class MemorySystem(ConsolidationMixin):
         ``where`` and ``diversity``; not with ``expand`` or ``boost``."""
         if lexical is not None and not isinstance(query, str):
             raise ValueError("a lexical search needs the query's text")
-        if where is not None:
-            where = self._where(where)
-        mmr = self._mmr(limit, diversity, fetch_k, expand, boost, lexical)
-        if mmr is not None and "lexical" in mmr:
-            mmr = dict(mmr, query_text=query)
+        spec = self._spec(limit, where, diversity, fetch_k, expand, boost, lexical)
         with tracer.stage("embed_query", self._device):
             q = self._get_embedding(query)
         with self._graph_lock:
             with tracer.stage("search", self._device):
-                if mmr is not None:
-                    kw = mmr if where is None else dict(mmr, where=where)
-                    ids = self.vector_store.search_nodes(q, user_id=self.user_id, limit=limit, **kw)
-                elif where is None:
-                    ids = self.vector_store.search_nodes(q, user_id=self.user_id, limit=limit)
-                else:
-                    ids = self.vector_store.search_nodes(q, user_id=self.user_id, limit=limit, where=where)
+                kw = {} if spec is None else spec.kwargs(query_text=query)
+                ids = self.vector_store.search_nodes(q, user_id=self.user_id, limit=limit, **kw)
             return [n for n in (self.buffer.get_node(i) for i in ids) if n is not None]
 
     def search_memories_batch(self, queries: List[str], limit: int = 5, where=None, diversity=None,
@@ -717,11 +663,9 @@ class MemorySystem(ConsolidationMixin):
         over the tenant's HBM rows -- and one row -> Node mapping. ``where``,
         ``diversity``, ``fetch_k``, ``expand``, ``boost``, ``lexical``: one
         setting for the whole batch (see :meth:`search_memories`)."""
-        if where is not None:
-            where = self._where(where)
-        mmr = self._mmr(limit, diversity, fetch_k, expand, boost, lexical)
+        spec = self._spec(limit, where, diversity, fetch_k, expand, boost, lexical)
         t0 = time.perf_counter()
-        out = self._search_finish(self._search_submit(queries, limit, where, mmr))
+        out = self._search_finish(self._search_submit(queries, limit, spec))
         self._count_search(len(out), (time.perf_counter() - t0) * 1e3)
         return out
 
@@ -741,32 +685,28 @@ class MemorySystem(ConsolidationMixin):
         ``search_memories_batch``. ``where``, ``diversity``, ``fetch_k``,
         ``expand``, ``boost``, ``lexical``: one setting for all batches (a
         boost's ``now`` is read once, for the whole stream)."""
-        if where is not None:
-            where = self._where(where)
-        mmr = self._mmr(limit, diversity, fetch_k, expand, boost, lexical)
+        spec = self._spec(limit, where, diversity, fetch_k, expand, boost, lexical)
         pending = collections.deque()
         for qs in batches:
-            pending.append(self._search_submit(qs, limit, where, mmr))
+            pending.append(self._search_submit(qs, limit, spec))
             if len(pending) > STREAM_DEPTH:
                 yield self._search_finish(pending.popleft())
         while pending:
             yield self._search_finish(pending.popleft())
 
-    def _search_submit(self, queries, limit: int, where=None, mmr=None):
+    def _search_submit(self, queries, limit: int, spec=None):
         """Enqueue embed + store search; returns a handle for _search_finish.
         With the graph-bound store the result rows stay on the device and come
         back with one async copy into pinned memory (no host sync here; a
         lexical search uploads its term tables from pageable memory, a copy the
         host waits for)."""
         queries = list(queries)
-        lex = mmr is not None and "lexical" in mmr
-        if lex:  # the queries' terms, on the host
+        terms = None
+        if spec is not None and spec.lexical is not None:  # the queries' terms, on the host
             from .lexical import as_query_terms
             if not all(isinstance(q, str) for q in queries):
                 raise ValueError("a lexical search needs the queries' text")
-            gmmr = dict(mmr, query_terms=as_query_terms(queries)) if queries else mmr
-        else:
-            gmmr = mmr
+            terms = as_query_terms(queries) if queries else None
         with tracer.stage("embed_query", self._device):
             embs = self._batch_embed_any(queries)
         with self._graph_lock:
@@ -788,16 +728,8 @@ class MemorySystem(ConsolidationMixin):
                     with tracer.stage("search", self._device):
                         # rows the graph does not hold as nodes are skipped (reference
                         # :1467-1472): marked on the device (by the re-rank kernel), so
-                        # mapping needs no mirror
-                        if mmr is not None:  # (the pool search marks non-node rows: they take no pick)
-                            _, rows = g.store_search(embs, int(limit), getattr(self.store, "metric", "l2"),
-                                                     node_rows=True, where=where, **gmmr)
-                        elif where is None:
-                            _, rows = g.store_search(embs, int(limit), getattr(self.store, "metric", "l2"),
-                                                     node_rows=True)
-                        else:  # (every row a filtered search returns is a node)
-                            _, rows = g.store_search(embs, int(limit), getattr(self.store, "metric", "l2"),
-                                                     where=where)
+                        # mapping needs no mirror (a pool search marks them too: they take no pick)
+                        _, rows = g._search(embs, int(limit), getattr(self.store, "metric", "l2"), True, spec, terms)
                     if rows.is_cuda:
                         # the rows stay on the device until _search_finish copies them to
                         # pageable host memory on a stream that waits for THIS search only
@@ -808,7 +740,7 @@ class MemorySystem(ConsolidationMixin):
                         return ("rows_dev", g, rows, ev, g.row_epoch)
                     return ("rows", g, rows, None, g.row_epoch)
         with tracer.stage("search", self._device):
-            return ("ids", None, self._search_batch(embs, limit, where, mmr, queries), None, 0)
+            return ("ids", None, self._search_batch(embs, limit, spec, queries), None, 0)
 
     def _search_finish(self, h) -> List[List[Node]]:
         kind_, g0, data, ev, epoch = h  # (the row epoch searched under: a compaction may run before the finish)

@@ -34,6 +34,7 @@ import torch
 from ..index.arena import VectorArena
 from ..store.colstore import EDGE_SCHEMA, NODE_SCHEMA, PROFILE_SCHEMA, ColumnarTable
 from ..utils.device import default_device
+from .search_spec import SearchSpec
 
 
 def _json(v, default):
@@ -279,25 +280,35 @@ class HBMStore:
             r["metadata"] = _unjson(r.get("metadata"), {})
         return rows
 
-    def _filter_needs_graph(self, user_id: str):
-        raise NotImplementedError(
-            f"a filtered search (where=) needs the tenant's graph attached to the store; {user_id!r} has none")
+    @staticmethod
+    def _spec(limit, texts, n: int, **options) -> Optional[SearchSpec]:
+        """The options of a search as a SearchSpec (None: a plain search); a
+        lexical search needs ``texts``, one string per query of the ``n``."""
+        spec = SearchSpec.of(limit, **options)
+        if spec is not None and spec.lexical is not None and (
+                texts is None or isinstance(texts, str) or len(texts) != n
+                or not all(isinstance(t, str) for t in texts)):
+            raise ValueError("a lexical search needs the queries' texts, one per query: pass query_text= / "
+                             "query_texts=")
+        return spec
 
-    def _mmr_needs_graph(self, user_id: str):
-        raise NotImplementedError(
-            f"a diverse search (diversity=) needs the tenant's graph attached to the store; {user_id!r} has none")
-
-    def _expand_needs_graph(self, user_id: str):
-        raise NotImplementedError(
-            f"an expanded search (expand=) needs the tenant's graph attached to the store; {user_id!r} has none")
-
-    def _lexical_needs_graph(self, user_id: str):
-        raise NotImplementedError(
-            f"a lexical search (lexical=) needs the tenant's graph attached to the store; {user_id!r} has none")
-
-    def _boost_needs_graph(self, user_id: str):
-        raise NotImplementedError(
-            f"a boosted search (boost=) needs the tenant's graph attached to the store; {user_id!r} has none")
+    def _graph_ids(self, embs, user_id: str, limit: int, spec, texts) -> Optional[List[List[str]]]:
+        """One id list per row of ``embs`` [M, D] from the tenant's attached
+        graph; None when it has none (a plain search is the arena's then, and
+        every option needs the graph's columns, rows, links or contents)."""
+        g = self._graphs.get(user_id)
+        if g is None:
+            if spec is not None:
+                spec.needs(f"the tenant's graph attached to the store; {user_id!r} has none")
+            return None
+        Q = embs if torch.is_tensor(embs) else torch.as_tensor(np.asarray(embs, dtype=np.float32))
+        if len(Q) == 0:
+            return []
+        with g.lock:  # the tenant's graph lock: a consolidation may be writing
+            if g.dim is None or Q.shape[-1] != g.dim:
+                return [[] for _ in range(len(Q))]
+            return g._search_ids(Q, int(limit), self.metric, spec,
+                                 None if spec is None or spec.lexical is None else list(texts))
 
     def search_nodes(self, query_emb, user_id: str = "default", limit: int = 5, where=None, diversity=None,
                      fetch_k=None, expand=None, boost=None, lexical=None, query_text=None) -> List[str]:
@@ -311,39 +322,14 @@ class HBMStore:
         salience, use and recency (core/boost.py). ``lexical`` with
         ``query_text`` (the query's text): keyword and hybrid search
         (core/lexical.py)."""
-        if lexical is not None:
-            from .lexical import LexicalSearch
-            lexical = LexicalSearch.coerce(lexical)
-            if expand is not None or boost is not None:
-                raise NotImplementedError("lexical= does not compose with expand= or boost=")
-            if not isinstance(query_text, str):
-                raise ValueError("a lexical search needs the query's text: pass query_text=")
+        spec = self._spec(limit, [query_text], 1, where=where, diversity=diversity, fetch_k=fetch_k, expand=expand,
+                          boost=boost, lexical=lexical)
         if query_emb is None or len(query_emb) == 0:
             return []
-        g = self._graphs.get(user_id)
-        if lexical is not None and g is None:
-            self._lexical_needs_graph(user_id)
-        if where is not None and g is None:
-            self._filter_needs_graph(user_id)
-        mmr = diversity is not None or fetch_k is not None
-        if mmr and g is None:
-            self._mmr_needs_graph(user_id)
-        if expand is not None and g is None:
-            self._expand_needs_graph(user_id)
-        if boost is not None and g is None:
-            self._boost_needs_graph(user_id)
-        if g is not None:
-            q = query_emb if torch.is_tensor(query_emb) else torch.from_numpy(
-                np.asarray(query_emb, dtype=np.float32))
-            with g.lock:  # the tenant's graph lock: a consolidation may be writing
-                if g.dim is None or q.shape[-1] != g.dim:
-                    return []
-                if lexical is not None:
-                    return g.search_ids(q, int(limit), self.metric, where, diversity, fetch_k, lexical=lexical,
-                                        query_terms=[query_text])[0]
-                if mmr or expand is not None or boost is not None:
-                    return g.search_ids(q, int(limit), self.metric, where, diversity, fetch_k, expand, boost)[0]
-                return g.search_ids(q, int(limit), self.metric, where)[0]
+        hits = self._graph_ids(query_emb[None] if torch.is_tensor(query_emb) else [query_emb], user_id, limit, spec,
+                               [query_text])
+        if hits is not None:
+            return hits[0]
         with self._lock:  # writers (add/delete/replace) mutate the arena in place
             a = self._arena(user_id)
             if len(a) == 0 or a.dim != len(query_emb):
@@ -358,40 +344,11 @@ class HBMStore:
         ``diversity``, ``fetch_k``, ``expand``, ``boost``: one setting for the
         whole batch (see :meth:`search_nodes`). ``lexical`` with
         ``query_texts``: the queries' texts, one per embedding."""
-        if lexical is not None:
-            from .lexical import LexicalSearch
-            lexical = LexicalSearch.coerce(lexical)
-            if expand is not None or boost is not None:
-                raise NotImplementedError("lexical= does not compose with expand= or boost=")
-            if query_texts is None or isinstance(query_texts, str) or len(query_texts) != len(query_embs) \
-                    or not all(isinstance(t, str) for t in query_texts):
-                raise ValueError("a lexical search needs the queries' texts, one per query: pass query_texts=")
-        g = self._graphs.get(user_id)
-        if lexical is not None and g is None:
-            self._lexical_needs_graph(user_id)
-        if where is not None and g is None:
-            self._filter_needs_graph(user_id)
-        mmr = diversity is not None or fetch_k is not None
-        if mmr and g is None:
-            self._mmr_needs_graph(user_id)
-        if expand is not None and g is None:
-            self._expand_needs_graph(user_id)
-        if boost is not None and g is None:
-            self._boost_needs_graph(user_id)
-        if g is not None:
-            Q = query_embs if torch.is_tensor(query_embs) else torch.as_tensor(
-                np.asarray(query_embs, dtype=np.float32))
-            if len(Q) == 0:
-                return []
-            with g.lock:
-                if g.dim is None or Q.shape[-1] != g.dim:
-                    return [[] for _ in range(len(Q))]
-                if lexical is not None:
-                    return g.search_ids(Q, int(limit), self.metric, where, diversity, fetch_k, lexical=lexical,
-                                        query_terms=list(query_texts))
-                if mmr or expand is not None or boost is not None:
-                    return g.search_ids(Q, int(limit), self.metric, where, diversity, fetch_k, expand, boost)
-                return g.search_ids(Q, int(limit), self.metric, where)
+        spec = self._spec(limit, query_texts, len(query_embs), where=where, diversity=diversity, fetch_k=fetch_k,
+                          expand=expand, boost=boost, lexical=lexical)
+        hits = self._graph_ids(query_embs, user_id, limit, spec, query_texts)
+        if hits is not None:
+            return hits
         with self._lock:
             a = self._arena(user_id)
             if len(a) == 0 or len(query_embs) == 0:
@@ -402,23 +359,10 @@ class HBMStore:
                            fetch_k=None, expand=None, boost=None, lexical=None) -> List[List[str]]:
         """Multi-tenant batch: query i searches tenant ``user_ids[i]`` only, all
         in one kernel launch (serving many users per GPU, BASELINE config 3).
-        Filters, diverse selection, graph expansion and boosts are not
-        supported here (``where``, ``diversity``, ``fetch_k``, ``expand`` and
-        ``boost`` raise)."""
-        from ..index.arena import multi_arena_search
-        if where is not None:
-            raise NotImplementedError("search_nodes_multi does not take a filter; search each tenant with where=")
-        if diversity is not None or fetch_k is not None:
-            raise NotImplementedError("search_nodes_multi does not select by diversity; search each tenant with "
-                                      "diversity=")
-        if expand is not None:
-            raise NotImplementedError("search_nodes_multi does not expand along links; search each tenant with "
-                                      "expand=")
-        if boost is not None:
-            raise NotImplementedError("search_nodes_multi does not boost; search each tenant with boost=")
-        if lexical is not None:
-            raise NotImplementedError("search_nodes_multi does not search by keyword; search each tenant with "
-                                      "lexical=")
+        The search options are not supported here (``where``, ``diversity``,
+        ``fetch_k``, ``expand``, ``boost`` and ``lexical`` raise)."""
+        SearchSpec.refuse("search_nodes_multi", where=where, diversity=diversity, fetch_k=fetch_k, expand=expand,
+                          boost=boost, lexical=lexical)
         if len(user_ids) == 0:
             return []
         with self._lock:

@@ -131,24 +131,19 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
                                ("until", until), ("accessed_since", accessed_since),
                                ("min_access_count", min_access_count), ("super_nodes", super_nodes),
                                ("exclude_ids", _csv(exclude_ids))) if v is not None}
-    kw = {"where": where} if where else {}
-    if diversity is not None or fetch_k is not None:
-        kw.update(diversity=diversity, fetch_k=fetch_k)
     expand = {k: v for k, v in (("hops", hops), ("fanout", fanout), ("graph_weight", graph_weight)) if v is not None}
-    if expand:
-        kw.update(expand=expand)
     if boost is not None:
         from ..core.boost import MemoryBoost
-        b = MemoryBoost.coerce(float(boost)).to_dict()
+        boost = MemoryBoost.coerce(float(boost)).to_dict()
         if boost_recency_scale is not None:
-            b["recency_scale"] = boost_recency_scale
-        kw.update(boost=b)
+            boost["recency_scale"] = boost_recency_scale
     if lexical is not None:
-        lx = {"alpha": lexical}
+        lexical = {"alpha": lexical}
         if lexical_pool is not None:
-            lx["pool"] = lexical_pool
-        kw.update(lexical=lx)
-    hits = _ms.search_memories(q, limit=limit, **kw)
+            lexical["pool"] = lexical_pool
+    # (an option that is None is an option not given)
+    hits = _ms.search_memories(q, limit=limit, where=where or None, diversity=diversity, fetch_k=fetch_k,
+                               expand=expand or None, boost=boost, lexical=lexical)
     return [{"id": n.id, "content": n.content, "salience": n.salience, "shard": n.shard_key} for n in hits]
 
 

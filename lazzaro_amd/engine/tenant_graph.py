@@ -2493,77 +2493,88 @@ class TenantGraph:
         alpha * normalised BM25`` over the union of the nearest and the best
         keyword matches; memories only. With ``diversity`` it is the pool
         search; with ``expand`` or ``boost`` it raises."""
-        if lexical is not None:
-            from ..core.lexical import LexicalSearch
-            lexical = LexicalSearch.coerce(lexical)
-            if expand is not None or boost is not None:
-                raise NotImplementedError("lexical= does not compose with expand= or boost=")
-            if query_terms is None:
-                raise ValueError("a lexical search needs the queries' text: pass query_terms=")
-            if diversity is not None or fetch_k is not None:
-                return self._store_search_mmr(Q, k, metric, node_rows, where, diversity, fetch_k, lexical=lexical,
-                                              query_terms=query_terms)
-            return self._store_search_lex(Q, k, metric, where, lexical, query_terms)
-        if boost is not None:
-            from ..core.boost import MemoryBoost
-            boost = MemoryBoost.coerce(boost).at()  # (``now`` is read once, here)
-        if diversity is not None or fetch_k is not None:
-            return self._store_search_mmr(Q, k, metric, node_rows, where, diversity, fetch_k, expand, boost)
-        if expand is not None:
-            return self.store_search_expand(Q, k, metric, where, expand, boost)[:2]
-        if boost is not None:
-            with self.on_stream():
-                self.boosted_searches += 1
-                if where is not None:
-                    return self._store_search_where(Q, k, metric, where, boost)
-                if self.n == 0 or self.dim is None:
-                    return self._store_search(Q, k, metric)
-                # a plan-like bias holder: the flat routes of _store_search, never the IVF-PQ index
-                # (its candidate stage cannot see the prior)
-                return self._store_search(Q, k, metric, False, self._boost_plan(boost, metric))
-        if where is not None:
-            with self.on_stream():
-                return self._store_search_where(Q, k, metric, where)
-        with self.on_stream():
-            s, r = self._store_search(Q, k, metric, node_rows)
-            if node_rows and not self._nodes_marked:
-                r = torch.where((r >= 0) & (self.kind[r.clamp_min(0)] == NODE), r, torch.full_like(r, -1))
-            self._nodes_marked = False
-            return s, r
+        from ..core.search_spec import SearchSpec
+        spec = SearchSpec.of(k, where, diversity, fetch_k, expand, boost, lexical)  # (a boost's ``now`` is read here)
+        return self._search(Q, int(k), metric, node_rows, spec, query_terms)
 
-    _nodes_marked = False  # the last _store_search already marked non-node rows (re-rank kernel)
+    def _search(self, Q, k: int, metric: str, node_rows: bool, spec, query_terms=None):
+        """:meth:`store_search` of a validated ``core.search_spec.SearchSpec``
+        (None: the plain search). The options compose here and nowhere else:
+        diversity picks from the pool that the search of the other options
+        returns; an expansion starts from the seeds of a boosted, filtered or
+        plain search; a lexical search fuses its keyword pool with a filtered
+        or plain dense one. The inner searches come back through here with
+        the options they keep."""
+        if spec is None:
+            with self.on_stream():
+                return self._store_search(Q, k, metric, node_rows)
+        if spec.lexical is not None and query_terms is None:
+            raise ValueError("a lexical search needs the queries' text: pass query_terms=")
+        if spec.diversity is not None:
+            return self._store_search_mmr(Q, k, metric, node_rows, spec, query_terms)
+        if spec.lexical is not None:
+            return self._store_search_lex(Q, k, metric, spec, query_terms)
+        if spec.expand is not None:
+            return self._store_search_expand(Q, k, metric, spec)[:2]
+        with self.on_stream():
+            if spec.boost is None:
+                return self._store_search_where(Q, k, metric, spec.where)
+            self.boosted_searches += 1
+            if spec.where is not None:
+                return self._store_search_where(Q, k, metric, spec.where, spec.boost)
+            if self.n == 0 or self.dim is None:
+                return self._store_search(Q, k, metric)
+            # a plan-like bias holder: the flat routes of _store_search, never the IVF-PQ index
+            # (its candidate stage cannot see the prior)
+            return self._store_search(Q, k, metric, False, self._boost_plan(spec.boost, metric))
+
+    def _queries(self, Q):
+        """``Q`` as the fp32 [M, D] device tensor, and whether there is
+        nothing to search: no rows, or rows of another width."""
+        Qf = Q.to(self.device, torch.float32)
+        if Qf.dim() == 1:
+            Qf = Qf[None, :]
+        return Qf, self.n == 0 or self.dim is None or Qf.shape[1] != self.dim
+
+    def _no_hits(self, M: int, k: int):
+        """(scores, rows) of a search that found nothing: (-inf, -1)."""
+        return (torch.full((M, k), NEG_INF, device=self.device),
+                torch.full((M, k), -1, dtype=torch.long, device=self.device))
+
+    @staticmethod
+    def _unit_queries(Qf):
+        """The queries at unit length (a zero query stays zero): cosine."""
+        qn = Qf.norm(dim=1, keepdim=True)
+        return Qf / torch.where(qn > 0, qn, torch.ones_like(qn))
+
+    def _nodes_only(self, r):
+        """``r`` with the rows that are not graph nodes set to -1."""
+        return torch.where((r >= 0) & (self.kind[r.clamp_min(0)] == NODE), r, torch.full_like(r, -1))
 
     mmr_searches = 0
 
-    def _store_search_mmr(self, Q, k, metric, node_rows, where, diversity, fetch_k, expand=None, boost=None,
-                          lexical=None, query_terms=None):
-        """:meth:`store_search` with ``diversity``: the pool is the plain
-        search at ``k = fetch_k`` (default ``max(16, 2 k)``, at most
-        MAX_FETCH_K = 64) by whatever route that takes, ``node_rows`` and
-        ``where`` passed through (with ``expand``, the expanded search at
-        ``k = fetch_k`` and its blended scores; with ``boost``, the boosted
-        search at ``k = fetch_k`` and its boosted scores; with ``lexical``,
-        the fused search at ``k = fetch_k`` and its blends); rows it marked -1 are not
+    def _store_search_mmr(self, Q, k, metric, node_rows, spec, query_terms=None):
+        """:meth:`store_search` with ``diversity``: the pool is the search of
+        the other options at ``k = fetch_k`` (default ``max(16, 2 k)``, at
+        most MAX_FETCH_K = 64) by whatever route that takes, ``node_rows``
+        passed through -- the plain or filtered search, or with ``expand``
+        the expanded search and its blended scores, with ``boost`` the
+        boosted search and its boosted scores, with ``lexical`` the fused
+        search and its blends; rows it marked -1 are not
         candidates. The ``k`` picks are greedy maximal marginal relevance
         over the pool's fp32 rows (ops.mmr_ops.mmr_select: cosine relevance
         and cosine redundancy whatever the metric, ties to the lower row),
         returned in pick order with the pool's own scores gathered, (-inf,
         -1) once the pool ran out. No host synchronisation of its own."""
         from ..ops.mmr_ops import mmr_select, pool_size
-        k = int(k)
-        F = pool_size(k, diversity, fetch_k)
-        if lexical is not None:
-            s, r = self.store_search(Q, F, metric, node_rows, where, lexical=lexical, query_terms=query_terms)
-        else:
-            s, r = self.store_search(Q, F, metric, node_rows, where, expand=expand, boost=boost)
+        F = pool_size(k, spec.diversity, spec.fetch_k)
+        s, r = self._search(Q, F, metric, node_rows, spec.only("where", "expand", "boost", "lexical"), query_terms)
         self.mmr_searches += 1
         with self.on_stream():
-            Qf = Q.to(self.device, torch.float32)
-            if Qf.dim() == 1:
-                Qf = Qf[None, :]
-            if self.n == 0 or self.dim is None or Qf.shape[1] != self.dim:
-                return s[:, :k], r[:, :k]  # (nothing was searched: all padding)
-            pick, _ = mmr_select(self.emb32[: self.n], Qf, r, k, float(diversity))
+            Qf, nothing = self._queries(Q)
+            if nothing:
+                return s[:, :k], r[:, :k]  # (all padding)
+            pick, _ = mmr_select(self.emb32[: self.n], Qf, r, k, spec.diversity)
             ok = pick >= 0
             p = pick.long().clamp_min(0)
             return (torch.where(ok, torch.gather(s, 1, p), torch.full_like(s[:, :k], NEG_INF)),
@@ -2588,26 +2599,24 @@ class TenantGraph:
         the row's own, else the row whose link carried it. The CSR is cached
         per edge version; rebuilding it after an edge change synchronises
         with the host. Nothing else here does."""
-        from ..core.expand import GraphExpand
-        from ..ops.expand_ops import expand_select, pool_bound
-        k = int(k)
-        sp = GraphExpand.coerce(expand)
-        pool_bound(sp, k)
-        _, seeds = self.store_search(Q, sp.seed_k, metric, True, where, boost=boost)
+        from ..core.search_spec import SearchSpec
+        if expand is None:
+            raise ValueError("expand settings are required")
+        return self._store_search_expand(Q, int(k), metric, SearchSpec.of(k, where, expand=expand, boost=boost))
+
+    def _store_search_expand(self, Q, k, metric, spec):
+        from ..ops.expand_ops import expand_select
+        sp = spec.expand
+        _, seeds = self._search(Q, sp.seed_k, metric, True, spec.only("where", "boost"))
         self.expanded_searches += 1
-        dev = self.device
-        Qf = Q.to(dev, torch.float32)
-        if Qf.dim() == 1:
-            Qf = Qf[None, :]
-        M = Qf.shape[0]
+        Qf, nothing = self._queries(Q)
+        if nothing:  # (all padding)
+            s, pad = self._no_hits(Qf.shape[0], k)
+            return s, pad, pad.clone()
         n = self.n
-        if n == 0 or self.dim is None or Qf.shape[1] != self.dim:  # (nothing was searched: all padding)
-            pad = torch.full((M, k), -1, dtype=torch.long, device=dev)
-            return torch.full((M, k), NEG_INF, device=dev), pad, pad.clone()
-        if where is not None:
-            from ..core.filters import MemoryFilter
+        if spec.where is not None:
             with self.on_stream():
-                bias = self._filter_plan(MemoryFilter.coerce(where), metric == "l2").bias  # (the seed search's plan)
+                bias = self._filter_plan(spec.where, metric == "l2").bias  # (the seed search's plan)
         else:
             bias = self.store_bias("l2" if metric == "l2" else "ip")
         csr = self.csr()
@@ -2649,15 +2658,14 @@ class TenantGraph:
         """The lexical leg alone: per query the ``k`` (<= 64) memories passing
         ``where`` with the largest BM25 score (ops/lex_ops.py), (scores [M, k],
         rows [M, k]), descending, ties to the lower row, (-inf, -1) padded."""
-        from ..ops.lex_ops import NEG_INF as _NI, _check_params, lex_topk
+        from ..ops.lex_ops import _check_params, lex_topk
         from ..core.lexical import as_query_terms
         k = int(k)
         _check_params(k, k1, b, 1.0)
         qt = as_query_terms(texts_or_terms)
         M = qt.shape[0]
         if self.n == 0:
-            return (torch.full((M, k), _NI, device=self.device),
-                    torch.full((M, k), -1, dtype=torch.long, device=self.device))
+            return self._no_hits(M, k)
         with self.on_stream():
             self.lexical_searches += 1
             lx = self.lexicon()
@@ -2665,7 +2673,7 @@ class TenantGraph:
             return lex_topk(lx.slots[:n], lx.dl[:n], self._lex_bias(metric, where), qt, lx.weights(qt), k, k1, b,
                             lx.avgdl)
 
-    def _store_search_lex(self, Q, k, metric, where, lexical, query_terms):
+    def _store_search_lex(self, Q, k, metric, spec, query_terms):
         """:meth:`store_search` with ``lexical``. Candidates: the dense pool
         -- the plain search at ``k = pool`` with ``node_rows=True`` and
         ``where`` passed through, by whatever route that takes (skipped at
@@ -2681,25 +2689,21 @@ class TenantGraph:
         host waits for."""
         from ..core.lexical import as_query_terms
         from ..ops.lex_ops import lex_fuse, lex_topk
-        k = int(k)
-        lexical.check_limit(k)
-        dev = self.device
-        Qf = Q.to(dev, torch.float32)
-        if Qf.dim() == 1:
-            Qf = Qf[None, :]
+        lexical, where = spec.lexical, spec.where
+        Qf, nothing = self._queries(Q)
         M = Qf.shape[0]
         qt = as_query_terms(query_terms)
         if qt.shape[0] != M:
             raise ValueError(f"{M} queries but the terms of {qt.shape[0]}")
+        if nothing:  # (all padding)
+            return self._no_hits(M, k)
         n = self.n
-        if n == 0 or self.dim is None or Qf.shape[1] != self.dim:  # (nothing to search: all padding)
-            return (torch.full((M, k), NEG_INF, device=dev), torch.full((M, k), -1, dtype=torch.long, device=dev))
         if self.emb32 is None:
             raise NotImplementedError("a lexical search needs the tenant's fp32 rows")
         P = lexical.pool
         dense = None
         if lexical.alpha < 1.0:
-            _, dense = self.store_search(Q, P, metric, True, where)
+            _, dense = self._search(Q, P, metric, True, spec.only("where"))
         with self.on_stream():
             self.lexical_searches += 1
             lx = self.lexicon()
@@ -2895,8 +2899,7 @@ class TenantGraph:
         Routes: no passing row -> all -1, no scan; on the GPU (L2, IP,
         cosine over unit rows), while rows x query tiles stays within
         FILTER_SPARSE_MAX_ROWS -> the indexed fp32 scan of the listed rows +
-        the exact re-rank (its result never consults ``_nodes_marked``: every
-        listed row is a node); otherwise the dense flow of
+        the exact re-rank (every listed row is a node); otherwise the dense flow of
         :meth:`_store_search` with the plan's bias as its row mask. Masking
         an IVF-PQ index's candidates afterwards would lose recall in
         proportion to the selectivity, so a tenant with an index takes these
@@ -2914,17 +2917,14 @@ class TenantGraph:
         from ..core.filters import MemoryFilter
         flt = MemoryFilter.coerce(where)
         n = self.n
-        dev = self.device
-        Qf = Q.to(dev, torch.float32)
-        if Qf.dim() == 1:
-            Qf = Qf[None, :]
+        Qf, nothing = self._queries(Q)
         M = Qf.shape[0]
         self.filtered_searches += 1
-        if n == 0 or self.dim is None or Qf.shape[1] != self.dim:
-            return self._store_search(Qf, k, metric)
+        if nothing:
+            return self._no_hits(M, k)
         plan = self._filter_plan(flt, metric == "l2")
         if plan.count == 0:
-            return (torch.full((M, k), NEG_INF, device=dev), torch.full((M, k), -1, dtype=torch.long, device=dev))
+            return self._no_hits(M, k)
         if boost is not None:
             plan = self._boost_plan(boost, metric, flt, plan)
         # (the indexed scan reads every listed row once per tile of 8 queries)
@@ -2933,8 +2933,7 @@ class TenantGraph:
             from ..ops.filter_ops import gather_topk
             self.filtered_sparse += 1
             if metric == "cosine":
-                qn = Qf.norm(dim=1, keepdim=True)
-                Qf = Qf / torch.where(qn > 0, qn, torch.ones_like(qn))
+                Qf = self._unit_queries(Qf)
             _, cand = gather_topk(self.emb32, plan.rows, plan.count, Qf, CAND_SLOTS, plan.bias,
                                   2.0 if metric == "l2" else 1.0)
             return self._rerank_store(Qf, cand, k, metric, plan.bias)
@@ -2943,8 +2942,7 @@ class TenantGraph:
                 and n <= FILTER_ANN_MAX_SCALE * plan.count:
             self.filtered_ann += 1
             if metric == "cosine":
-                qn = Qf.norm(dim=1, keepdim=True)
-                Qf = Qf / torch.where(qn > 0, qn, torch.ones_like(qn))
+                Qf = self._unit_queries(Qf)
             cand = self._ann_candidates(Qf, max(cfg.get("rerank", 1024), k), cfg, plan)
             return self._rerank_store(Qf, cand, k, metric, plan.bias)
         return self._store_search(Qf, k, metric, False, plan)
@@ -2952,16 +2950,12 @@ class TenantGraph:
     def _store_search(self, Q, k, metric, node_rows=False, plan=None):
         from ..ops.search import flat_topk
         n = self.n
-        dev = self.device
-        Qf = Q.to(dev, torch.float32)
-        if Qf.dim() == 1:
-            Qf = Qf[None, :]
+        Qf, nothing = self._queries(Q)
         M = Qf.shape[0]
-        if n == 0 or self.dim is None or Qf.shape[1] != self.dim:
-            return self._pad_k(torch.zeros((M, 0), device=dev), torch.zeros((M, 0), dtype=torch.long, device=dev), k)
+        if nothing:
+            return self._no_hits(M, k)
         if metric == "cosine":
-            qn = Qf.norm(dim=1, keepdim=True)
-            Qf = Qf / torch.where(qn > 0, qn, torch.ones_like(qn))
+            Qf = self._unit_queries(Qf)
         bias = self.store_bias("l2" if metric == "l2" else "ip") if plan is None else plan.bias
         alpha = 2.0 if metric == "l2" else 1.0
         cfg = self.ann_cfg
@@ -2969,14 +2963,15 @@ class TenantGraph:
             # IVF-PQ candidates (the store's index="ivfpq"), re-ranked exactly
             # in fp32 against this graph's rows with the store's row mask
             cand = self._ann_candidates(Qf, max(cfg.get("rerank", 1024), k), cfg)
-            return self._rerank_store(Qf, cand, k, metric, bias)
+            return self._rerank_store(Qf, cand, k, metric, bias, node_rows)
         kc = CAND_SLOTS  # the fp32 re-rank sees 16 bf16 candidates for every k <= 16
         if self.on_gpu and k <= CAND_SLOTS and (metric != "cosine" or self.unit_rows()) \
                 and M * n >= KERNEL_MIN_WORK // 16:
             q16 = self._q16(Qf)
             narrow = LOWP_NARROW and self.emb8 is not None and self.emb8.dtype == torch.int8
             if self.lean and not self.unit_rows():
-                return self._exact_store(Qf, k, metric, bias)  # (no bf16 rows to scan; the error model needs unit rows)
+                # (no bf16 rows to scan; the error model needs unit rows)
+                return self._exact_store(Qf, k, metric, bias, node_rows)
             if self.lean or (self.emb8 is not None and self.unit_rows() and (M >= LOWP_MIN_Q or narrow)
                              and n >= LOWP_MIN_ROWS):
                 if self.emb8.dtype == torch.int8:
@@ -2992,7 +2987,7 @@ class TenantGraph:
             self.wide_searches += 1
             _, cand = self._i8_candidates_wide(Qf, self._q16(Qf), WIDE_CAND_SLOTS, bias, alpha)
             return self._rerank_store(Qf, cand, k, metric, bias, node_rows)
-        return self._exact_store(Qf, k, metric, bias)
+        return self._exact_store(Qf, k, metric, bias, node_rows)
 
     wide_k = False  # opt-in (HBMStore(wide_k=True) / MemoryConfig.wide_k): see _wide_route
     wide_searches = 0
@@ -3196,7 +3191,7 @@ class TenantGraph:
             return dot / torch.where(nrm > 0, nrm, torch.ones_like(nrm)) + bias
         return dot + bias
 
-    def _exact_store(self, Qf, k, metric, bias, chunk: int = 1 << 18):
+    def _exact_store(self, Qf, k, metric, bias, node_rows=False, chunk: int = 1 << 18):
         n = self.n
         M = Qf.shape[0]
         best_s = torch.full((M, 0), NEG_INF, device=self.device)
@@ -3208,12 +3203,12 @@ class TenantGraph:
             cs, ci = torch.cat([best_s, s], 1), torch.cat([best_i, idx], 1)
             o = torch.sort(cs, dim=1, descending=True, stable=True).indices[:, :k]
             best_s, best_i = torch.gather(cs, 1, o), torch.gather(ci, 1, o)
-        return self._pad_k(best_s, best_i, k)
+        s, r = self._pad_k(best_s, best_i, k)
+        return s, self._nodes_only(r) if node_rows else r
 
     def _rerank_store(self, Qf, cand, k, metric, bias, node_rows=False):
         if self.on_gpu and RERANK_KERNEL and 0 < cand.shape[1] <= 64 and metric in ("l2", "ip", "cosine"):
             from ..ops.tenant_ops import store_rerank
-            self._nodes_marked = bool(node_rows)
             return store_rerank(Qf, self.emb32, self.sqn, bias, cand, k, metric,
                                 kind=self.kind if node_rows else None)
         valid = cand >= 0
@@ -3224,19 +3219,19 @@ class TenantGraph:
         o = torch.argsort(key, dim=1, stable=True)
         s, cand = torch.gather(s, 1, o), torch.gather(cand, 1, o)
         o = torch.sort(s, dim=1, descending=True, stable=True).indices[:, :k]
-        return self._pad_k(torch.gather(s, 1, o), torch.gather(cand, 1, o), k)
+        s, r = self._pad_k(torch.gather(s, 1, o), torch.gather(cand, 1, o), k)
+        return s, self._nodes_only(r) if node_rows else r  # (the kernel above marks them itself)
 
     def search_ids(self, Q, k: int, metric: str = "l2", where=None, diversity=None, fetch_k=None,
                    expand=None, boost=None, lexical=None, query_terms=None) -> List[List[str]]:
-        if lexical is not None:
-            _, r = self.store_search(Q, k, metric, node_rows=True, where=where, diversity=diversity, fetch_k=fetch_k,
-                                     expand=expand, boost=boost, lexical=lexical, query_terms=query_terms)
-        elif diversity is not None or fetch_k is not None or expand is not None or boost is not None:
-            # (node rows only: a row the caller would drop must not take a pick)
-            _, r = self.store_search(Q, k, metric, node_rows=True, where=where, diversity=diversity, fetch_k=fetch_k,
-                                     expand=expand, boost=boost)
-        else:
-            _, r = self.store_search(Q, k, metric, where=where)
+        from ..core.search_spec import SearchSpec
+        return self._search_ids(Q, int(k), metric, SearchSpec.of(k, where, diversity, fetch_k, expand, boost, lexical),
+                                query_terms)
+
+    def _search_ids(self, Q, k, metric, spec, query_terms=None) -> List[List[str]]:
+        # (with an option, node rows only: a row the caller would drop must not take a pick; the plain
+        # search returns the store's rows, ghosts included, and the caller drops them)
+        _, r = self._search(Q, k, metric, spec is not None, spec, query_terms)
         ids = self.ids
         return [[ids[x] for x in row if x >= 0] for row in r.cpu().tolist()]
 
@@ -3621,7 +3616,6 @@ class TenantGraph:
         self._mirror.clear()
         self._csr, self._csr_version = None, -1
         self._boost_state = T.BoostState()
-        self._nodes_marked = False
         self._tcode, self._tcode_n, self._tcode_dirty = None, 0, None  # rebuilt by the next type filter
         self._filter_plans = None
         self._boost_cols = None

@@ -37,6 +37,7 @@ from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from ..core.search_spec import SearchSpec
 from . import routing
 from .comm import Communicator
 from .placement import tenant_rank
@@ -692,17 +693,6 @@ class DistributedMemoryService:
                 lk.release()
 
     # ------------------------------------------------------------ columnar search (routing.py)
-    @staticmethod
-    def _no_mmr(what: str, diversity, fetch_k, expand=None, boost=None, lexical=None) -> None:
-        if lexical is not None:
-            raise NotImplementedError(f"DistributedMemoryService.{what} does not search by keyword (lexical=)")
-        if diversity is not None or fetch_k is not None:
-            raise NotImplementedError(f"DistributedMemoryService.{what} does not select by diversity (diversity=)")
-        if expand is not None:
-            raise NotImplementedError(f"DistributedMemoryService.{what} does not expand along links (expand=)")
-        if boost is not None:
-            raise NotImplementedError(f"DistributedMemoryService.{what} does not boost (boost=)")
-
     def search_routed(self, users: Sequence[str], queries, limit=5, where=None, diversity=None,
                       fetch_k=None, expand=None, boost=None, lexical=None) -> "routing.RoutedHits":
         """SPMD batched search_memories with tensors on the wire: ``queries``
@@ -710,9 +700,8 @@ class DistributedMemoryService:
         embedding tensor [n, D]; each goes to ``users[q]``'s owner in one
         all-to-all and its (score, row) hits come back in one more. Returns a
         :class:`~.routing.RoutedHits` in the caller's order."""
-        if where is not None:
-            raise NotImplementedError("DistributedMemoryService.search_routed takes no filter (where=)")
-        DistributedMemoryService._no_mmr("search_routed", diversity, fetch_k, expand, boost, lexical)
+        SearchSpec.refuse("DistributedMemoryService.search_routed", where=where, diversity=diversity, fetch_k=fetch_k,
+                          expand=expand, boost=boost, lexical=lexical)
         Q = self._embed_front(queries)
         return routing.search_routed(self, list(users), Q, limit)
 
@@ -725,9 +714,8 @@ class DistributedMemoryService:
         two all-to-alls, the owners' store searches), so the encoder runs
         under the search instead of after it. Every rank must iterate alike.
         Yields one :class:`~.routing.RoutedHits` per batch, in order."""
-        if where is not None:
-            raise NotImplementedError("DistributedMemoryService.search_routed_stream takes no filter (where=)")
-        DistributedMemoryService._no_mmr("search_routed_stream", diversity, fetch_k, expand, boost, lexical)
+        SearchSpec.refuse("DistributedMemoryService.search_routed_stream", where=where, diversity=diversity,
+                          fetch_k=fetch_k, expand=expand, boost=boost, lexical=lexical)
         dev = self.comm.device
         side = None
         if dev.type == "cuda":
@@ -763,9 +751,8 @@ class DistributedMemoryService:
                             fetch_k=None, expand=None, boost=None, lexical=None) -> "routing.GlobalHits":
         """SPMD: this rank's queries against every resident tenant of every
         rank (all-gather of queries, local search, one all-to-all back)."""
-        if where is not None:
-            raise NotImplementedError("DistributedMemoryService.search_global_batch takes no filter (where=)")
-        DistributedMemoryService._no_mmr("search_global_batch", diversity, fetch_k, expand, boost, lexical)
+        SearchSpec.refuse("DistributedMemoryService.search_global_batch", where=where, diversity=diversity,
+                          fetch_k=fetch_k, expand=expand, boost=boost, lexical=lexical)
         return routing.search_global_batch(self, self._embed_front(queries), limit)
 
     def resolve(self, hits: "routing.RoutedHits") -> List[List[Dict]]:
@@ -808,9 +795,8 @@ class DistributedMemoryService:
         """Top-``limit`` over every resident tenant of every rank for one
         query vector (exact store scores: -|q-x|^2 for L2). Returns the same
         list of {user_id, node...} dicts on every rank."""
-        if where is not None:
-            raise NotImplementedError("DistributedMemoryService.search_global takes no filter (where=)")
-        DistributedMemoryService._no_mmr("search_global", diversity, fetch_k, expand, boost, lexical)
+        SearchSpec.refuse("DistributedMemoryService.search_global", where=where, diversity=diversity, fetch_k=fetch_k,
+                          expand=expand, boost=boost, lexical=lexical)
         comm = self.comm
         cands = []
         for user, ms in self.systems.items():

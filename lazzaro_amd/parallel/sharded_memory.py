@@ -81,6 +81,7 @@ import torch
 
 from ..core.consolidation import (DECAY_RATE, LINK_THRESHOLD, LINK_TOPK, MIN_FACT_LEN, PROFILE_CONTENTS,
                                   _host_pinned, batch_dedupe, batch_link_plan, salience_decayed)
+from ..core.search_spec import SearchSpec
 from ..engine.tenant_graph import GHOST, NODE, SHARD_MASK, TYPE_MASK, TYPE_SHIFT, _seg_min, _seg_sum_count
 from ..ops import tenant_ops as T
 from ..utils.tracing import tracer
@@ -580,17 +581,8 @@ class ShardedMemorySystem:
         re-rank, L2) over its rows, the (score, owner, row) lists are merged
         (ties -> lower node number) and the winners' node dicts are returned
         to the rank that asked. Returns this rank's results."""
-        if where is not None:
-            raise NotImplementedError("ShardedMemorySystem.search_memories_batch takes no filter (where=)")
-        if diversity is not None or fetch_k is not None:
-            raise NotImplementedError("ShardedMemorySystem.search_memories_batch does not select by diversity")
-        if expand is not None:
-            raise NotImplementedError("ShardedMemorySystem.search_memories_batch does not expand along links (expand=)")
-        if boost is not None:
-            raise NotImplementedError("ShardedMemorySystem.search_memories_batch does not boost (boost=)")
-        if lexical is not None:
-            raise NotImplementedError("ShardedMemorySystem.search_memories_batch does not search by keyword (lexical=)")
-
+        SearchSpec.refuse("ShardedMemorySystem.search_memories_batch", where=where, diversity=diversity,
+                          fetch_k=fetch_k, expand=expand, boost=boost, lexical=lexical)
         g = self.g
         dev = self.device
         qs = list(queries)
