@@ -742,6 +742,85 @@ class MemorySystem(ConsolidationMixin):
         with tracer.stage("search", self._device):
             return ("ids", None, self._search_batch(embs, limit, spec, queries), None, 0)
 
+    def search_memories_fused(self, queries: List[str], limit: int = 5, fuse="rrf", where=None, expand=None,
+                              boost=None, lexical=None, weights=None) -> List[Node]:
+        """Multi-query search: ONE ranked list for a group of 1 .. 16
+        sub-queries -- the user's sentence, a rewritten question, the previous
+        turn, a hypothetical answer. Every sub-query is searched with the
+        inner options (``where``, ``expand``, ``boost``, ``lexical``; see
+        :meth:`search_memories`) at ``limit = pool`` and the union of the
+        pools is scored on the device by ``fuse`` (core/fuse.py): ``"rrf"``,
+        reciprocal rank fusion ``sum_j w_j / (rrf_k + rank_j)`` over the pools
+        that hold a memory, or ``"mean"``, the weighted mean cosine over all
+        sub-queries; a dict or a :class:`QueryFusion` sets ``pool`` (default
+        16), ``rrf_k`` (60) and per-position ``weights``. The ``limit`` best
+        come back, ties to the lower row. ``weights``: this group's, one per
+        sub-query. There is no ``diversity=`` here."""
+        if isinstance(queries, str):
+            raise ValueError("search_memories_fused takes a list of sub-queries")
+        out = self.search_memories_fused_batch([queries], limit, fuse, where, expand, boost, lexical,
+                                               None if weights is None else [weights])
+        return list(out[0])
+
+    def search_memories_fused_batch(self, query_groups: List[List[str]], limit: int = 5, fuse="rrf", where=None,
+                                    expand=None, boost=None, lexical=None, weights=None) -> List[List[Node]]:
+        """:meth:`search_memories_fused` for many groups: ONE embedding call
+        for all sub-queries, one store search, one fusion launch, and one
+        result list per group. ``weights`` in a :class:`QueryFusion` apply
+        per position and need equal group sizes; otherwise pass
+        ``weights=[[...], ...]``, one sequence per group."""
+        from .fuse import QueryFusion
+        fu = QueryFusion.coerce(fuse)
+        if fu is None:
+            raise ValueError("fuse settings are required")
+        groups = [[g] if isinstance(g, str) else list(g) for g in query_groups]
+        sizes = [len(g) for g in groups]
+        fu.check(limit, sizes)
+        fu.group_weights(sizes, weights)
+        spec = self._spec(fu.pool, where, None, None, expand, boost, lexical)
+        if not self._store_binds_graph():
+            raise NotImplementedError("a search with fuse= needs a store bound to the tenant graph (HBMStore)")
+        queries = [q for g in groups for q in g]
+        if spec is not None and spec.lexical is not None and not all(isinstance(q, str) for q in queries):
+            raise ValueError("a lexical search needs the queries' text")
+        t0 = time.perf_counter()
+        out = self._search_finish(self._fused_submit(queries, sizes, limit, fu, spec, weights))
+        self._count_search(len(out), (time.perf_counter() - t0) * 1e3)
+        return out
+
+    def _fused_submit(self, queries, sizes, limit: int, fu, spec, weights):
+        """:meth:`_search_submit` of a fused search: the same handle shapes,
+        one entry per group."""
+        offsets = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        if not queries:
+            return ("ids", None, [[] for _ in sizes], None, 0)
+        opts = {} if spec is None else spec.kwargs(query_terms=queries)
+        with tracer.stage("embed_query", self._device):
+            embs = self._batch_embed_any(queries)
+        with self._graph_lock:
+            g = self.graph
+            if not torch.is_tensor(embs):
+                embs = torch.as_tensor(np.asarray(embs, dtype=np.float32))
+            if g.dim is None or embs.shape[-1] != g.dim:
+                return ("ids", None, [[] for _ in sizes], None, 0)
+            overlap = SEARCH_OVERLAP and embs.is_cuda and g.on_gpu
+            if overlap:  # (as _search_submit: the search and its result copy run on the graph's stream)
+                cur = torch.cuda.current_stream(g.device)
+                g.stream.wait_stream(cur)
+                embs.record_stream(g.stream)
+                ctx = torch.cuda.stream(g.stream)
+            else:
+                ctx = contextlib.nullcontext()
+            with ctx:
+                with tracer.stage("search", self._device):
+                    _, rows, _ = g.store_search_fused(embs, offsets, int(limit), getattr(self.store, "metric", "l2"),
+                                                      fu, weights=weights, **opts)
+                if rows.is_cuda:
+                    ev = torch.cuda.Event(blocking=BLOCKING_EVENTS)
+                    ev.record()
+                    return ("rows_dev", g, rows, ev, g.row_epoch)
+                return ("rows", g, rows, None, g.row_epoch)
+
     def _search_finish(self, h) -> List[List[Node]]:
         kind_, g0, data, ev, epoch = h  # (the row epoch searched under: a compaction may run before the finish)
         if kind_ == "rows_dev":
@@ -819,6 +898,7 @@ class MemorySystem(ConsolidationMixin):
                 "mmr_searches": g.mmr_searches, "expanded_searches": g.expanded_searches,
                 "boosted_searches": g.boosted_searches, "boost_columns_built": g.boost_columns_built,
                 "lexical_searches": g.lexical_searches,
+                "fused_searches": g.fused_searches, "fused_groups": g.fused_groups,
                 "lexicon_rows": 0 if g._lexicon is None else g._lexicon.covered,
                 "lexicon_builds": 0 if g._lexicon is None else g._lexicon.builds,
                 "wide_searches": g.wide_searches, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,

@@ -355,6 +355,44 @@ class HBMStore:
                 return [[] for _ in range(len(query_embs))]
             return a.search(query_embs, int(limit), self.metric)
 
+    def search_nodes_fused(self, query_embs, offsets, user_id: str = "default", limit: int = 5, fuse="rrf",
+                           where=None, expand=None, boost=None, lexical=None, query_texts=None,
+                           weights=None) -> List[List[str]]:
+        """Multi-query search: ``offsets`` cuts ``query_embs`` [M, D] into
+        groups of 1 .. 16 sub-queries and every group returns ONE id list,
+        its sub-queries' pools fused on the device by ``fuse`` (``"rrf"``,
+        ``"mean"``, a dict or a ``core.fuse.QueryFusion``;
+        TenantGraph.store_search_fused). ``where``, ``expand``, ``boost``,
+        ``lexical`` with ``query_texts`` (one per sub-query): the inner
+        options of every pool search. ``weights``: one sequence per group.
+        The tenant's graph must be attached: the arena has no pools of graph
+        rows to fuse."""
+        from .fuse import QueryFusion
+        from ..ops.fuse_ops import group_sizes
+        fu = QueryFusion.coerce(fuse)
+        if fu is None:
+            raise ValueError("fuse settings are required")
+        sizes = group_sizes(offsets, len(query_embs))
+        fu.check(limit, sizes)
+        fu.group_weights(sizes, weights)
+        spec = self._spec(fu.pool, query_texts, len(query_embs), where=where, expand=expand, boost=boost,
+                          lexical=lexical)
+        g = self._graphs.get(user_id)
+        if g is None:
+            if spec is not None:
+                spec.needs(f"the tenant's graph attached to the store; {user_id!r} has none")
+            raise NotImplementedError(f"a search with fuse= needs the tenant's graph attached to the store; "
+                                      f"{user_id!r} has none")
+        Q = query_embs if torch.is_tensor(query_embs) else torch.as_tensor(np.asarray(query_embs, dtype=np.float32))
+        if len(Q) == 0:
+            return [[] for _ in sizes]
+        with g.lock:  # the tenant's graph lock: a consolidation may be writing
+            if g.dim is None or Q.shape[-1] != g.dim:
+                return [[] for _ in sizes]
+            opts = {} if spec is None else spec.kwargs(query_terms=list(query_texts) if query_texts is not None
+                                                       else None)
+            return g.search_ids_fused(Q, offsets, int(limit), self.metric, fu, weights=weights, **opts)
+
     def search_nodes_multi(self, query_embs, user_ids: Sequence[str], limit: int = 5, where=None, diversity=None,
                            fetch_k=None, expand=None, boost=None, lexical=None) -> List[List[str]]:
         """Multi-tenant batch: query i searches tenant ``user_ids[i]`` only, all

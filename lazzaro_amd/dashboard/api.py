@@ -10,9 +10,9 @@ Extra: ``GET /api/search?q=&limit=`` (on-device vector search) and
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import List, Optional
 
-from fastapi import FastAPI, Request
+from fastapi import FastAPI, Query, Request
 from fastapi.responses import HTMLResponse
 
 app = FastAPI(title="Lazzaro MI355X Memory Dashboard")
@@ -109,7 +109,8 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
                  diversity: Optional[float] = None, fetch_k: Optional[int] = None,
                  hops: Optional[int] = None, fanout: Optional[int] = None, graph_weight: Optional[float] = None,
                  boost: Optional[float] = None, boost_recency_scale: Optional[float] = None,
-                 lexical: Optional[float] = None, lexical_pool: Optional[int] = None):
+                 lexical: Optional[float] = None, lexical_pool: Optional[int] = None,
+                 also: Optional[List[str]] = Query(None), fuse: Optional[str] = None):
     """``MemoryFilter`` fields as optional query parameters (the set-valued
     ones comma separated); none given: the unfiltered search. ``diversity``
     (0 .. 1) and ``fetch_k``: results picked for diversity from the
@@ -123,7 +124,11 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
     day; given alone it changes nothing). ``lexical`` (``alpha`` in 0 .. 1):
     keyword and hybrid search over the memories' words (``lexical=``,
     core/lexical.py); ``lexical_pool``: its candidate pool (default 16; given
-    alone it changes nothing)."""
+    alone it changes nothing). ``also`` (repeatable): further sub-queries --
+    ``q`` and every ``also`` form one group whose pools are fused into one
+    list (``MemorySystem.search_memories_fused``, core/fuse.py) by ``fuse``
+    (``rrf``, the default, or ``mean``); without ``also`` nothing changes.
+    ``diversity`` / ``fetch_k`` do not apply to a fused search."""
     if not _ms:
         return []
     where = {k: v for k, v in (("types", _csv(types)), ("shard_keys", _csv(shard_keys)),
@@ -141,6 +146,12 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
         lexical = {"alpha": lexical}
         if lexical_pool is not None:
             lexical["pool"] = lexical_pool
+    if also:
+        if diversity is not None or fetch_k is not None:
+            raise ValueError("diversity= / fetch_k= do not apply to a fused search (also=)")
+        hits = _ms.search_memories_fused([q] + list(also), limit=limit, fuse=fuse or "rrf", where=where or None,
+                                         expand=expand or None, boost=boost, lexical=lexical)
+        return [{"id": n.id, "content": n.content, "salience": n.salience, "shard": n.shard_key} for n in hits]
     # (an option that is None is an option not given)
     hits = _ms.search_memories(q, limit=limit, where=where or None, diversity=diversity, fetch_k=fetch_k,
                                expand=expand or None, boost=boost, lexical=lexical)

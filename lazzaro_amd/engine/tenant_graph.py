@@ -2714,8 +2714,68 @@ class TenantGraph:
             return lex_fuse(self.emb32[:n], Qf, dense, lp, lx.slots, lx.dl, qt, w, lexical.alpha, k, lexical.k1,
                             lexical.b, avgdl)
 
+    # ---- multi-query search
+    fused_searches = fused_groups = 0
+
+    def store_search_fused(self, Q, offsets, k, metric: str = "l2", fuse="rrf", where=None, expand=None, boost=None,
+                           lexical=None, query_terms=None, weights=None):
+        """One ranked list per GROUP of sub-queries: ``offsets`` (``NG + 1``
+        ascending entries from 0 to ``M``, on the host) cuts the ``M`` rows of
+        ``Q`` into groups of 1 .. 16. Every sub-query's pool is the search of
+        the inner options (``where``, ``expand``, ``boost``, ``lexical`` with
+        ``query_terms``, one entry per sub-query) at ``k = fuse.pool`` with
+        ``node_rows=True`` by whatever route that takes -- one call for all
+        ``M``; the union of a group's pools is scored by ``fuse`` (``"rrf"``,
+        ``"mean"``, a dict or a ``core.fuse.QueryFusion``;
+        ops.fuse_ops.fuse_select holds the contract) and the ``k`` best come
+        back, descending, ties to the lower row. ``weights``: one sequence
+        per group (default: the fusion's per-position weights, else 1).
+        ``mean`` scores by cosine over the fp32 rows whatever the metric, and
+        the inner options decide the pools only. There is no ``diversity``
+        here: its relevance needs one query vector. Returns (scores [NG, k],
+        rows [NG, k], support [NG, k]) with (-inf, -1, 0) beyond the
+        candidate count. No host synchronisation of its own."""
+        from ..core.fuse import QueryFusion
+        from ..core.search_spec import SearchSpec
+        from ..ops.fuse_ops import fuse_select, group_sizes
+        fu = QueryFusion.coerce(fuse)
+        if fu is None:
+            raise ValueError("fuse settings are required")
+        M = 1 if Q.dim() == 1 else Q.shape[0]
+        sizes = group_sizes(offsets, M)
+        k = int(k) if isinstance(k, (int, np.integer)) and not isinstance(k, bool) else k
+        fu.check(k, sizes)
+        flat = fu.group_weights(sizes, weights)
+        spec = SearchSpec.of(fu.pool, where, expand=expand, boost=boost, lexical=lexical)
+        NG = len(sizes)
+        if M == 0:
+            s, r = self._no_hits(NG, k)
+            return s, r, torch.zeros((NG, k), dtype=torch.int32, device=self.device)
+        _, pools = self._search(Q, fu.pool, metric, True, spec, query_terms)
+        self.fused_searches += 1
+        self.fused_groups += NG
+        Qf, nothing = self._queries(Q)
+        if nothing:  # (all padding)
+            s, r = self._no_hits(NG, k)
+            return s, r, torch.zeros((NG, k), dtype=torch.int32, device=self.device)
+        if fu.mode == "mean" and self.emb32 is None:
+            raise NotImplementedError("a mean-fused search needs the tenant's fp32 rows")
+        n = self.n
+        with self.on_stream():
+            X = self.emb32[:n] if fu.mode == "mean" else None
+            rows, scores, support, _ = fuse_select(X, Qf if X is not None else None, offsets, pools, k, fu, flat, n)
+        return scores, rows, support
+
+    def search_ids_fused(self, Q, offsets, k, metric: str = "l2", fuse="rrf", where=None, expand=None, boost=None,
+                         lexical=None, query_terms=None, weights=None) -> List[List[str]]:
+        """:meth:`store_search_fused`, one id list per group."""
+        _, r, _ = self.store_search_fused(Q, offsets, k, metric, fuse, where, expand, boost, lexical, query_terms,
+                                          weights)
+        ids = self.ids
+        return [[ids[x] for x in row if x >= 0] for row in r.cpu().tolist()]
+
     # ---- boosted search
-    _boost_cols = None  # OrderedDict: column key -> FilterPlan holding the boosted column (LRU, BOOST_COLUMN_CACHE)
+    _boost_cols = None # OrderedDict: column key -> FilterPlan holding the boosted column (LRU, BOOST_COLUMN_CACHE)
     boosted_searches = boost_columns_built = 0
 
     def boost_bias(self, boost, metric: str = "l2", where=None, now: Optional[float] = None) -> torch.Tensor:
