@@ -3068,12 +3068,8 @@ class TenantGraph:
     def _i8_candidates_wide(self, Qf: torch.Tensor, q16: torch.Tensor, kc: int, bias: torch.Tensor, alpha: float):
         """:meth:`_i8_candidates` for 16 < kc <= 64 (ops.search.flat_topk_i8_wide),
         under the same two margins."""
-        from ..ops.search import NARROW_MAX_Q, flat_topk_i8_wide
-        q8, qs, margin, margin_rig = self._i8_query(q16, alpha)
-        if not self._lowp_exact(Qf.shape[0] < NARROW_MAX_Q):
-            margin_rig = margin
-        else:
-            margin = margin_rig
+        from ..ops.search import flat_topk_i8_wide
+        q8, qs, margin, margin_rig = self._i8_margins(Qf, q16, alpha)
         return flat_topk_i8_wide(self.emb8, self.rs8, q8, qs, self._scan_rows(self.n, Qf), q16, kc, bias=bias,
                                  alpha=alpha, margin=margin, margin_rig=margin_rig)
 
@@ -3168,10 +3164,19 @@ class TenantGraph:
     def _i8_candidates(self, Qf: torch.Tensor, q16: torch.Tensor, kc: int, bias: torch.Tensor, alpha: float):
         """Store-search candidates from the int8 scan (``emb8`` / ``rs8``),
         re-scored from the bf16 rows above the error cut and certified per
-        query (ops.search.flat_topk_i8), with the worst-case margin of
-        :meth:`_i8_query` (the result is the bf16 search's for ANY data) or
-        the statistical one (wide batches by default, see LOWP_EXACT)."""
-        from ..ops.search import NARROW_MAX_Q, flat_topk_i8
+        query (ops.search.flat_topk_i8), under the margins of
+        :meth:`_i8_margins`."""
+        from ..ops.search import flat_topk_i8
+        q8, qs, margin, margin_rig = self._i8_margins(Qf, q16, alpha)
+        return flat_topk_i8(self.emb8, self.rs8, q8, qs, self._scan_rows(self.n, Qf), q16, kc, bias=bias,
+                            alpha=alpha, margin=margin, margin_rig=margin_rig)
+
+    def _i8_margins(self, Qf: torch.Tensor, q16: torch.Tensor, alpha: float):
+        """:meth:`_i8_query` with the margin choice of a store search: the
+        worst-case margin for both roles (the result is the bf16 search's for
+        ANY data) or the statistical one (wide batches by default, see
+        LOWP_EXACT). Returns (q8, qs, margin, margin_rig)."""
+        from ..ops.search import NARROW_MAX_Q
         q8, qs, margin, margin_rig = self._i8_query(q16, alpha)
         if not self._lowp_exact(Qf.shape[0] < NARROW_MAX_Q):
             margin_rig = margin
@@ -3182,8 +3187,7 @@ class TenantGraph:
             # |<q16, x16> - <q, x>| <= 2^-8 |q| |x| (both operands rounded to bf16)
             w = alpha * 2.0 ** -8 * Qf.norm(dim=1) * (1.0 + self.max_norm_dev)
             margin, margin_rig = (margin + w).contiguous(), (margin_rig + w).contiguous()
-        return flat_topk_i8(self.emb8, self.rs8, q8, qs, self._scan_rows(self.n, Qf), q16, kc, bias=bias,
-                            alpha=alpha, margin=margin, margin_rig=margin_rig)
+        return q8, qs, margin, margin_rig
 
     def _i8_query(self, q16: torch.Tensor, alpha: float):
         """int8 queries, per-query scales and the two error margins of the
