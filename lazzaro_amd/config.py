@@ -53,6 +53,10 @@ class MemoryConfig:
     ivf_filtered: bool = False            # ivfpq: filtered searches scan the passing rows of the probed lists
     wide_k: bool = False                  # store searches with 16 < k <= 64 take the certified int8 route
     lexical_slots: int = 16               # keyword search: term slots per memory in the lexicon (8, 16 or 32)
+    reranker: Optional[str] = None        # cross-encoder of rerank=: a config name (minilm-l6 ...), None: off
+    reranker_weights: Optional[str] = None  # safetensors path (HF BertForSequenceClassification layout)
+    reranker_vocab: Optional[str] = None  # vocab.txt of the re-ranker's tokenizer (hashed ids without one)
+    rerank_doc_tokens: int = 64           # body pieces kept per memory in the token column (32, 64 or 128)
     hierarchy_mode: str = "reference"     # reference (one mean super-node per shard) | kmeans (two-level)
     hierarchy_fine: int = 4096            # kmeans: fine clusters
     hierarchy_top: int = 64               # kmeans: top-level clusters

@@ -234,7 +234,10 @@ class MemorySystem(ConsolidationMixin):
         kw.setdefault("index", cfg.index)
         kw.setdefault("index_params", {"nlist": cfg.nlist, "nprobe": cfg.nprobe, "pq_m": cfg.pq_m,
                                        "ivf_min_rows": cfg.ivf_min_rows, "ivf_filtered": cfg.ivf_filtered,
-                                       "wide_k": cfg.wide_k, "lexical_slots": cfg.lexical_slots})
+                                       "wide_k": cfg.wide_k, "lexical_slots": cfg.lexical_slots,
+                                       "reranker": cfg.reranker, "reranker_weights": cfg.reranker_weights,
+                                       "reranker_vocab": cfg.reranker_vocab,
+                                       "rerank_doc_tokens": cfg.rerank_doc_tokens})
         kw.setdefault("hierarchy_mode", cfg.hierarchy_mode)
         kw.setdefault("hierarchy_params", {"fine": cfg.hierarchy_fine, "top": cfg.hierarchy_top,
                                            "every": cfg.hierarchy_every})
@@ -611,18 +614,21 @@ class MemorySystem(ConsolidationMixin):
         kind = g.flags_of(out)[0]
         return [NodeView.of(g, x) for x, k in zip(out, kind) if k == NODE]
 
-    def _spec(self, limit, where, diversity, fetch_k, expand, boost, lexical):
+    def _spec(self, limit, where, diversity, fetch_k, expand, boost, lexical, rerank=None):
         """The options of a search as a :class:`SearchSpec` (None: a plain
         search), validated before any work. Every option reads the bound
         tenant graph -- its HBM columns, fp32 rows, links or contents; a store
-        that holds its own rows has none of them."""
-        spec = SearchSpec.of(limit, where, diversity, fetch_k, expand, boost, lexical)
+        that holds its own rows has none of them. ``rerank`` needs a store
+        with a ``reranker``."""
+        spec = SearchSpec.of(limit, where, diversity, fetch_k, expand, boost, lexical, rerank)
         if spec is not None and not self._store_binds_graph():
             spec.needs("a store bound to the tenant graph (HBMStore)")
+        if spec is not None and spec.rerank is not None and getattr(self.store, "reranker", None) is None:
+            raise ValueError("rerank= needs a store with a reranker (index_params={'reranker': ...})")
         return spec
 
     def search_memories(self, query: str, limit: int = 5, where=None, diversity=None, fetch_k=None,
-                        expand=None, boost=None, lexical=None) -> List[Node]:
+                        expand=None, boost=None, lexical=None, rerank=None) -> List[Node]:
         """``where`` (a :class:`MemoryFilter` or a dict of its fields): only
         the memories passing it are searched -- the ``limit`` nearest AMONG
         them, not a post-filter of the nearest. ``diversity`` (0 .. 1): the
@@ -643,10 +649,18 @@ class MemorySystem(ConsolidationMixin):
         query's words against each memory's content, over the union of the
         ``pool`` nearest memories and the ``pool`` best keyword matches
         (core/lexical.py); 1.0 is keyword search alone. Composes with
-        ``where`` and ``diversity``; not with ``expand`` or ``boost``."""
+        ``where`` and ``diversity``; not with ``expand`` or ``boost``.
+        ``rerank`` (True, an int ``pool``, a dict or a :class:`CrossRerank`):
+        the search of the other options runs at ``limit = pool`` (default 16,
+        at most 64) and the store's cross-encoder reads the query together
+        with each memory of the pool; the ``limit`` largest classification
+        logits come back (core/crossenc.py). Needs a store with a
+        ``reranker``; composes with every option but ``diversity``."""
         if lexical is not None and not isinstance(query, str):
             raise ValueError("a lexical search needs the query's text")
-        spec = self._spec(limit, where, diversity, fetch_k, expand, boost, lexical)
+        if rerank is not None and rerank is not False and not isinstance(query, str):
+            raise ValueError("a re-ranked search needs the query's text")
+        spec = self._spec(limit, where, diversity, fetch_k, expand, boost, lexical, rerank)
         with tracer.stage("embed_query", self._device):
             q = self._get_embedding(query)
         with self._graph_lock:
@@ -656,14 +670,15 @@ class MemorySystem(ConsolidationMixin):
             return [n for n in (self.buffer.get_node(i) for i in ids) if n is not None]
 
     def search_memories_batch(self, queries: List[str], limit: int = 5, where=None, diversity=None,
-                              fetch_k=None, expand=None, boost=None, lexical=None) -> List[List[Node]]:
+                              fetch_k=None, expand=None, boost=None, lexical=None, rerank=None) -> List[List[Node]]:
         """Batched ``search_memories`` (reference :1460-1472 per query): one
         embedding call (a device tensor when the encoder is on-device), one
         store search -- the fused MFMA candidate scan plus an fp32 re-rank
         over the tenant's HBM rows -- and one row -> Node mapping. ``where``,
-        ``diversity``, ``fetch_k``, ``expand``, ``boost``, ``lexical``: one
-        setting for the whole batch (see :meth:`search_memories`)."""
-        spec = self._spec(limit, where, diversity, fetch_k, expand, boost, lexical)
+        ``diversity``, ``fetch_k``, ``expand``, ``boost``, ``lexical``,
+        ``rerank``: one setting for the whole batch (see
+        :meth:`search_memories`)."""
+        spec = self._spec(limit, where, diversity, fetch_k, expand, boost, lexical, rerank)
         t0 = time.perf_counter()
         out = self._search_finish(self._search_submit(queries, limit, spec))
         self._count_search(len(out), (time.perf_counter() - t0) * 1e3)
@@ -676,16 +691,18 @@ class MemorySystem(ConsolidationMixin):
         m["search_ms"] = m.get("search_ms", 0.0) + ms
 
     def search_memories_stream(self, batches: Iterable[List[str]], limit: int = 5, where=None, diversity=None,
-                               fetch_k=None, expand=None, boost=None, lexical=None):
+                               fetch_k=None, expand=None, boost=None, lexical=None, rerank=None):
         """Pipelined ``search_memories_batch`` for serving loops: batches i+1 ..
         i+STREAM_DEPTH are tokenised and their embed + scan enqueued on the
         device BEFORE the host waits for batch i and maps its rows to Nodes,
         so host work (tokenizer, result mapping) hides under device work.
         Yields one result list per input batch, in order; results equal
         ``search_memories_batch``. ``where``, ``diversity``, ``fetch_k``,
-        ``expand``, ``boost``, ``lexical``: one setting for all batches (a
-        boost's ``now`` is read once, for the whole stream)."""
-        spec = self._spec(limit, where, diversity, fetch_k, expand, boost, lexical)
+        ``expand``, ``boost``, ``lexical``, ``rerank``: one setting for all
+        batches (a boost's ``now`` is read once, for the whole stream; a
+        re-ranked search takes the queries' tokens on the host at submit and
+        reads 8 bytes back per chunk, which waits for that batch's pool)."""
+        spec = self._spec(limit, where, diversity, fetch_k, expand, boost, lexical, rerank)
         pending = collections.deque()
         for qs in batches:
             pending.append(self._search_submit(qs, limit, spec))
@@ -707,6 +724,12 @@ class MemorySystem(ConsolidationMixin):
             if not all(isinstance(q, str) for q in queries):
                 raise ValueError("a lexical search needs the queries' text")
             terms = as_query_terms(queries) if queries else None
+        tokens = None
+        if spec is not None and spec.rerank is not None:  # the queries' tokens, on the host
+            from ..ops.crossenc_ops import as_query_tokens
+            if not all(isinstance(q, str) for q in queries):
+                raise ValueError("a re-ranked search needs the queries' text")
+            tokens = as_query_tokens(queries, self.store.reranker_model(self._device).tokenizer) if queries else None
         with tracer.stage("embed_query", self._device):
             embs = self._batch_embed_any(queries)
         with self._graph_lock:
@@ -729,7 +752,8 @@ class MemorySystem(ConsolidationMixin):
                         # rows the graph does not hold as nodes are skipped (reference
                         # :1467-1472): marked on the device (by the re-rank kernel), so
                         # mapping needs no mirror (a pool search marks them too: they take no pick)
-                        _, rows = g._search(embs, int(limit), getattr(self.store, "metric", "l2"), True, spec, terms)
+                        _, rows = g._search(embs, int(limit), getattr(self.store, "metric", "l2"), True, spec, terms,
+                                            tokens)
                     if rows.is_cuda:
                         # the rows stay on the device until _search_finish copies them to
                         # pageable host memory on a stream that waits for THIS search only
@@ -743,7 +767,7 @@ class MemorySystem(ConsolidationMixin):
             return ("ids", None, self._search_batch(embs, limit, spec, queries), None, 0)
 
     def search_memories_fused(self, queries: List[str], limit: int = 5, fuse="rrf", where=None, expand=None,
-                              boost=None, lexical=None, weights=None) -> List[Node]:
+                              boost=None, lexical=None, weights=None, rerank=None) -> List[Node]:
         """Multi-query search: ONE ranked list for a group of 1 .. 16
         sub-queries -- the user's sentence, a rewritten question, the previous
         turn, a hypothetical answer. Every sub-query is searched with the
@@ -759,17 +783,20 @@ class MemorySystem(ConsolidationMixin):
         if isinstance(queries, str):
             raise ValueError("search_memories_fused takes a list of sub-queries")
         out = self.search_memories_fused_batch([queries], limit, fuse, where, expand, boost, lexical,
-                                               None if weights is None else [weights])
+                                               None if weights is None else [weights], rerank)
         return list(out[0])
 
     def search_memories_fused_batch(self, query_groups: List[List[str]], limit: int = 5, fuse="rrf", where=None,
-                                    expand=None, boost=None, lexical=None, weights=None) -> List[List[Node]]:
+                                    expand=None, boost=None, lexical=None, weights=None,
+                                    rerank=None) -> List[List[Node]]:
         """:meth:`search_memories_fused` for many groups: ONE embedding call
         for all sub-queries, one store search, one fusion launch, and one
         result list per group. ``weights`` in a :class:`QueryFusion` apply
         per position and need equal group sizes; otherwise pass
         ``weights=[[...], ...]``, one sequence per group."""
         from .fuse import QueryFusion
+        if rerank is not None and rerank is not False:
+            raise NotImplementedError("a fused search does not take rerank=: re-rank each query's own search")
         fu = QueryFusion.coerce(fuse)
         if fu is None:
             raise ValueError("fuse settings are required")
@@ -899,6 +926,8 @@ class MemorySystem(ConsolidationMixin):
                 "boosted_searches": g.boosted_searches, "boost_columns_built": g.boost_columns_built,
                 "lexical_searches": g.lexical_searches,
                 "fused_searches": g.fused_searches, "fused_groups": g.fused_groups,
+                "reranked_searches": g.reranked_searches, "rerank_pairs": g.rerank_pairs,
+                "token_column_builds": g.token_column_builds,
                 "lexicon_rows": 0 if g._lexicon is None else g._lexicon.covered,
                 "lexicon_builds": 0 if g._lexicon is None else g._lexicon.builds,
                 "wide_searches": g.wide_searches, "search_queries": sq, "search_qps": round(sq / (sms / 1e3), 1) if sms > 0 else 0.0,

@@ -56,7 +56,9 @@ class HBMStore:
     def __init__(self, db_dir: str = "db", device=None, metric: str = "l2",
                  consistency_interval: float = 0.5, keep_fp32: bool = True, index: str = "flat",
                  nlist: int = 4096, nprobe: int = 32, pq_m: int = 64, ivf_min_rows: int = 1_000_000,
-                 ivf_filtered: bool = False, wide_k: bool = False, lexical_slots: int = 16):
+                 ivf_filtered: bool = False, wide_k: bool = False, lexical_slots: int = 16,
+                 reranker: Optional[str] = None, reranker_weights: Optional[str] = None,
+                 reranker_vocab: Optional[str] = None, rerank_doc_tokens: int = 64):
         """index="ivfpq": a tenant arena with >= ivf_min_rows live rows is served
         by IVF-PQ candidates re-ranked exactly (smaller tenants stay exact flat).
         ivf_filtered: an attached tenant graph's filtered searches (``where=``)
@@ -65,9 +67,29 @@ class HBMStore:
         wide_k: an attached tenant graph serves searches with 16 < k <= 64 on the
         certified int8 candidate route (TenantGraph.wide_k); off: the exact fp32 scan.
         lexical_slots: the term slots per memory of an attached graph's lexicon
-        (keyword search, ``lexical=``): 8, 16 or 32."""
+        (keyword search, ``lexical=``): 8, 16 or 32.
+        reranker: the config name (models.encoder.CONFIGS) of the cross-encoder
+        that serves ``rerank=`` on an attached graph, None: off;
+        reranker_weights: a safetensors file in HF BertForSequenceClassification
+        naming (random-init without one); reranker_vocab: its vocab.txt (hashed
+        ids without one); rerank_doc_tokens: the body pieces kept per memory
+        in the token column, 32, 64 or 128."""
         if index not in ("flat", "ivfpq"):
             raise ValueError("index must be 'flat' or 'ivfpq'")
+        from .crossenc import MAX_VOCAB, check_doc_tokens
+        self.rerank_doc_tokens = check_doc_tokens(rerank_doc_tokens)
+        self.reranker = None
+        self._reranker_model = None
+        if reranker is not None:
+            from ..models.encoder import get_config
+            try:
+                cfg = get_config(reranker)
+            except KeyError as e:
+                raise ValueError(str(e)) from None
+            if cfg.vocab > MAX_VOCAB:
+                raise ValueError(f"the token column stores 16-bit ids: vocabulary {cfg.vocab} exceeds {MAX_VOCAB}")
+            self.reranker = cfg.name
+        self.reranker_weights, self.reranker_vocab = reranker_weights, reranker_vocab
         if int(lexical_slots) not in (8, 16, 32):
             raise ValueError(f"lexical_slots must be 8, 16 or 32 (got {lexical_slots})")
         self.lexical_slots = int(lexical_slots)
@@ -103,8 +125,22 @@ class HBMStore:
                 graph.wide_k = True
             if self.lexical_slots != 16:
                 graph.lexical_slots = self.lexical_slots
+            if self.reranker is not None:
+                graph.reranker = self.reranker_model(graph.device)
+                graph.rerank_doc_tokens = self.rerank_doc_tokens
             if self.index == "ivfpq":  # large tenants: IVF-PQ candidates + exact fp32 re-rank on the graph
                 graph.ann_cfg = dict(self.ivf_params, filtered=self.ivf_filtered)
+
+    def reranker_model(self, device=None):
+        """The store's cross-encoder (built on first use, shared by every
+        attached graph); None without ``reranker``."""
+        if self.reranker is None:
+            return None
+        if self._reranker_model is None:
+            from ..models.cross_encoder import CrossEncoder
+            self._reranker_model = CrossEncoder(self.reranker, device=device if device is not None else self.device,
+                                                weights=self.reranker_weights, vocab_file=self.reranker_vocab)
+        return self._reranker_model
 
     def detach(self, user_id: str) -> None:
         with self._lock:
@@ -280,16 +316,18 @@ class HBMStore:
             r["metadata"] = _unjson(r.get("metadata"), {})
         return rows
 
-    @staticmethod
-    def _spec(limit, texts, n: int, **options) -> Optional[SearchSpec]:
+    def _spec(self, limit, texts, n: int, **options) -> Optional[SearchSpec]:
         """The options of a search as a SearchSpec (None: a plain search); a
-        lexical search needs ``texts``, one string per query of the ``n``."""
+        lexical or a re-ranked search needs ``texts``, one string per query of
+        the ``n``, and a re-ranked one a store with a ``reranker``."""
         spec = SearchSpec.of(limit, **options)
-        if spec is not None and spec.lexical is not None and (
+        if spec is not None and spec.rerank is not None and self.reranker is None:
+            raise ValueError("rerank= needs a store with a reranker (HBMStore(reranker=...))")
+        if spec is not None and spec.needs_text and (
                 texts is None or isinstance(texts, str) or len(texts) != n
                 or not all(isinstance(t, str) for t in texts)):
-            raise ValueError("a lexical search needs the queries' texts, one per query: pass query_text= / "
-                             "query_texts=")
+            raise ValueError(f"a {'lexical' if spec.lexical is not None else 're-ranked'} search needs the queries' "
+                             "texts, one per query: pass query_text= / query_texts=")
         return spec
 
     def _graph_ids(self, embs, user_id: str, limit: int, spec, texts) -> Optional[List[List[str]]]:
@@ -308,10 +346,11 @@ class HBMStore:
             if g.dim is None or Q.shape[-1] != g.dim:
                 return [[] for _ in range(len(Q))]
             return g._search_ids(Q, int(limit), self.metric, spec,
-                                 None if spec is None or spec.lexical is None else list(texts))
+                                 None if spec is None or spec.lexical is None else list(texts),
+                                 None if spec is None or spec.rerank is None else list(texts))
 
     def search_nodes(self, query_emb, user_id: str = "default", limit: int = 5, where=None, diversity=None,
-                     fetch_k=None, expand=None, boost=None, lexical=None, query_text=None) -> List[str]:
+                     fetch_k=None, expand=None, boost=None, lexical=None, query_text=None, rerank=None) -> List[str]:
         """``where`` (a MemoryFilter or a dict of its fields): only the
         tenant's memories passing it are searched (core/filters.py).
         ``diversity`` / ``fetch_k``: the results are picked from the
@@ -321,9 +360,11 @@ class HBMStore:
         (core/expand.py). ``boost``: the best by closeness plus a prior from
         salience, use and recency (core/boost.py). ``lexical`` with
         ``query_text`` (the query's text): keyword and hybrid search
-        (core/lexical.py)."""
+        (core/lexical.py). ``rerank`` with ``query_text``: the pool of the
+        other options re-scored by the store's cross-encoder
+        (core/crossenc.py)."""
         spec = self._spec(limit, [query_text], 1, where=where, diversity=diversity, fetch_k=fetch_k, expand=expand,
-                          boost=boost, lexical=lexical)
+                          boost=boost, lexical=lexical, rerank=rerank)
         if query_emb is None or len(query_emb) == 0:
             return []
         hits = self._graph_ids(query_emb[None] if torch.is_tensor(query_emb) else [query_emb], user_id, limit, spec,
@@ -338,14 +379,14 @@ class HBMStore:
 
     def search_nodes_batch(self, query_embs, user_id: str = "default", limit: int = 5,
                            where=None, diversity=None, fetch_k=None, expand=None, boost=None, lexical=None,
-                           query_texts=None) -> List[List[str]]:
+                           query_texts=None, rerank=None) -> List[List[str]]:
         """Batched variant (one kernel launch for all queries). ``query_embs``
         may be a device tensor (kept on the device end to end). ``where``,
         ``diversity``, ``fetch_k``, ``expand``, ``boost``: one setting for the
-        whole batch (see :meth:`search_nodes`). ``lexical`` with
+        whole batch (see :meth:`search_nodes`). ``lexical`` / ``rerank`` with
         ``query_texts``: the queries' texts, one per embedding."""
         spec = self._spec(limit, query_texts, len(query_embs), where=where, diversity=diversity, fetch_k=fetch_k,
-                          expand=expand, boost=boost, lexical=lexical)
+                          expand=expand, boost=boost, lexical=lexical, rerank=rerank)
         hits = self._graph_ids(query_embs, user_id, limit, spec, query_texts)
         if hits is not None:
             return hits
@@ -357,7 +398,7 @@ class HBMStore:
 
     def search_nodes_fused(self, query_embs, offsets, user_id: str = "default", limit: int = 5, fuse="rrf",
                            where=None, expand=None, boost=None, lexical=None, query_texts=None,
-                           weights=None) -> List[List[str]]:
+                           weights=None, rerank=None) -> List[List[str]]:
         """Multi-query search: ``offsets`` cuts ``query_embs`` [M, D] into
         groups of 1 .. 16 sub-queries and every group returns ONE id list,
         its sub-queries' pools fused on the device by ``fuse`` (``"rrf"``,
@@ -369,6 +410,8 @@ class HBMStore:
         rows to fuse."""
         from .fuse import QueryFusion
         from ..ops.fuse_ops import group_sizes
+        if rerank is not None and rerank is not False:
+            raise NotImplementedError("a fused search does not take rerank=: re-rank each query's own search")
         fu = QueryFusion.coerce(fuse)
         if fu is None:
             raise ValueError("fuse settings are required")
@@ -394,13 +437,13 @@ class HBMStore:
             return g.search_ids_fused(Q, offsets, int(limit), self.metric, fu, weights=weights, **opts)
 
     def search_nodes_multi(self, query_embs, user_ids: Sequence[str], limit: int = 5, where=None, diversity=None,
-                           fetch_k=None, expand=None, boost=None, lexical=None) -> List[List[str]]:
+                           fetch_k=None, expand=None, boost=None, lexical=None, rerank=None) -> List[List[str]]:
         """Multi-tenant batch: query i searches tenant ``user_ids[i]`` only, all
         in one kernel launch (serving many users per GPU, BASELINE config 3).
         The search options are not supported here (``where``, ``diversity``,
-        ``fetch_k``, ``expand``, ``boost`` and ``lexical`` raise)."""
+        ``fetch_k``, ``expand``, ``boost``, ``lexical`` and ``rerank`` raise)."""
         SearchSpec.refuse("search_nodes_multi", where=where, diversity=diversity, fetch_k=fetch_k, expand=expand,
-                          boost=boost, lexical=lexical)
+                          boost=boost, lexical=lexical, rerank=rerank or None)
         if len(user_ids) == 0:
             return []
         with self._lock:

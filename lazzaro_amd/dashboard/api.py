@@ -110,6 +110,7 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
                  hops: Optional[int] = None, fanout: Optional[int] = None, graph_weight: Optional[float] = None,
                  boost: Optional[float] = None, boost_recency_scale: Optional[float] = None,
                  lexical: Optional[float] = None, lexical_pool: Optional[int] = None,
+                 rerank: Optional[bool] = None, rerank_pool: Optional[int] = None,
                  also: Optional[List[str]] = Query(None), fuse: Optional[str] = None):
     """``MemoryFilter`` fields as optional query parameters (the set-valued
     ones comma separated); none given: the unfiltered search. ``diversity``
@@ -124,11 +125,14 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
     day; given alone it changes nothing). ``lexical`` (``alpha`` in 0 .. 1):
     keyword and hybrid search over the memories' words (``lexical=``,
     core/lexical.py); ``lexical_pool``: its candidate pool (default 16; given
-    alone it changes nothing). ``also`` (repeatable): further sub-queries --
+    alone it changes nothing). ``rerank`` (true): the pool of the other
+    options is re-scored by the store's cross-encoder (``rerank=``,
+    core/crossenc.py); ``rerank_pool``: its pool (default 16; given alone it
+    changes nothing). ``also`` (repeatable): further sub-queries --
     ``q`` and every ``also`` form one group whose pools are fused into one
     list (``MemorySystem.search_memories_fused``, core/fuse.py) by ``fuse``
     (``rrf``, the default, or ``mean``); without ``also`` nothing changes.
-    ``diversity`` / ``fetch_k`` do not apply to a fused search."""
+    ``diversity`` / ``fetch_k`` / ``rerank`` do not apply to a fused search."""
     if not _ms:
         return []
     where = {k: v for k, v in (("types", _csv(types)), ("shard_keys", _csv(shard_keys)),
@@ -146,15 +150,18 @@ async def search(q: str, limit: int = 5, types: Optional[str] = None, shard_keys
         lexical = {"alpha": lexical}
         if lexical_pool is not None:
             lexical["pool"] = lexical_pool
+    rr = ({"pool": rerank_pool} if rerank_pool is not None else True) if rerank else None
     if also:
         if diversity is not None or fetch_k is not None:
             raise ValueError("diversity= / fetch_k= do not apply to a fused search (also=)")
+        if rr is not None:
+            raise ValueError("rerank= does not apply to a fused search (also=)")
         hits = _ms.search_memories_fused([q] + list(also), limit=limit, fuse=fuse or "rrf", where=where or None,
                                          expand=expand or None, boost=boost, lexical=lexical)
         return [{"id": n.id, "content": n.content, "salience": n.salience, "shard": n.shard_key} for n in hits]
     # (an option that is None is an option not given)
     hits = _ms.search_memories(q, limit=limit, where=where or None, diversity=diversity, fetch_k=fetch_k,
-                               expand=expand or None, boost=boost, lexical=lexical)
+                               expand=expand or None, boost=boost, lexical=lexical, rerank=rr)
     return [{"id": n.id, "content": n.content, "salience": n.salience, "shard": n.shard_key} for n in hits]
 
 

@@ -2462,7 +2462,7 @@ class TenantGraph:
 
     def store_search(self, Q: torch.Tensor, k: int, metric: str = "l2", node_rows: bool = False, where=None,
                      diversity: Optional[float] = None, fetch_k: Optional[int] = None, expand=None, boost=None,
-                     lexical=None, query_terms=None):
+                     lexical=None, query_terms=None, rerank=None, query_tokens=None):
         """The store's vector search over this tenant (reference
         ``LanceDBStore.search_nodes``: flat scan, L2 unless told otherwise,
         vector_store.py:132-140). fp32 scores -- -|q-x|^2 for L2, cosine, or
@@ -2492,12 +2492,18 @@ class TenantGraph:
         (:meth:`_store_search_lex`) -- the ``k`` best by ``(1 - alpha) * cos +
         alpha * normalised BM25`` over the union of the nearest and the best
         keyword matches; memories only. With ``diversity`` it is the pool
-        search; with ``expand`` or ``boost`` it raises."""
+        search; with ``expand`` or ``boost`` it raises.
+        ``rerank`` (True, an int pool, a dict or a ``core.crossenc.CrossRerank``)
+        with ``query_tokens`` (the queries' texts, or ``(ids [M, <= 64],
+        lens)``): the pool of the other options is re-scored by the store's
+        cross-encoder and the ``k`` largest logits come back
+        (:meth:`store_search_rerank`, which also returns the pool's logits);
+        the scores returned are the logits. With ``diversity`` it raises."""
         from ..core.search_spec import SearchSpec
-        spec = SearchSpec.of(k, where, diversity, fetch_k, expand, boost, lexical)  # (a boost's ``now`` is read here)
-        return self._search(Q, int(k), metric, node_rows, spec, query_terms)
+        spec = SearchSpec.of(k, where, diversity, fetch_k, expand, boost, lexical, rerank)  # (a boost's ``now`` is read here)
+        return self._search(Q, int(k), metric, node_rows, spec, query_terms, query_tokens)
 
-    def _search(self, Q, k: int, metric: str, node_rows: bool, spec, query_terms=None):
+    def _search(self, Q, k: int, metric: str, node_rows: bool, spec, query_terms=None, query_tokens=None):
         """:meth:`store_search` of a validated ``core.search_spec.SearchSpec``
         (None: the plain search). The options compose here and nowhere else:
         diversity picks from the pool that the search of the other options
@@ -2508,8 +2514,15 @@ class TenantGraph:
         if spec is None:
             with self.on_stream():
                 return self._store_search(Q, k, metric, node_rows)
+        if spec.rerank is not None:
+            if self.reranker is None:
+                raise ValueError("rerank= needs a store with a reranker (HBMStore(reranker=...))")
+            if query_tokens is None:
+                raise ValueError("a re-ranked search needs the queries' text: pass query_tokens=")
         if spec.lexical is not None and query_terms is None:
             raise ValueError("a lexical search needs the queries' text: pass query_terms=")
+        if spec.rerank is not None:
+            return self._store_search_rerank(Q, k, metric, spec, query_terms, query_tokens)[:2]
         if spec.diversity is not None:
             return self._store_search_mmr(Q, k, metric, node_rows, spec, query_terms)
         if spec.lexical is not None:
@@ -2635,6 +2648,8 @@ class TenantGraph:
         next lexical search."""
         if self._lexicon is not None:
             self._lexicon.rewritten(r)
+        if self._token_column is not None:
+            self._token_column.rewritten(r)
 
     def lexicon(self):
         """The tenant's lexicon, synced to rows [0, n) (built on first use)."""
@@ -2714,11 +2729,85 @@ class TenantGraph:
             return lex_fuse(self.emb32[:n], Qf, dense, lp, lx.slots, lx.dl, qt, w, lexical.alpha, k, lexical.k1,
                             lexical.b, avgdl)
 
+    # ---- cross-encoder re-ranking
+    reranker = None  # the store's models.cross_encoder.CrossEncoder (HBMStore(reranker=...)); None: off
+    rerank_doc_tokens = 64  # L: body pieces kept per memory in the token column (MemoryConfig.rerank_doc_tokens)
+    _token_column = None  # the derived token column (engine/token_column.py), built on the first re-ranked search
+    reranked_searches = rerank_pairs = 0
+
+    @property
+    def token_column_builds(self) -> int:
+        return 0 if self._token_column is None else self._token_column.builds
+
+    def token_column(self):
+        """The tenant's token column, synced to rows [0, n) (built on first
+        use; a new one when L or the tokenizer changed)."""
+        from .token_column import TokenColumn
+        ce = self.reranker
+        if ce is None:
+            raise ValueError("the token column needs a store with a reranker (HBMStore(reranker=...))")
+        col = self._token_column
+        if col is None or col.L != int(self.rerank_doc_tokens) or col.tokenizer is not ce.tokenizer:
+            builds = 0 if col is None else col.builds
+            col = self._token_column = TokenColumn(self, ce.tokenizer, int(self.rerank_doc_tokens), ce.cfg.vocab)
+            col.builds = builds
+        with self.on_stream():
+            return col.sync()
+
+    def store_search_rerank(self, Q, k, metric: str = "l2", rerank=True, query_tokens=None, where=None, expand=None,
+                            boost=None, lexical=None, query_terms=None):
+        """:meth:`store_search` with ``rerank``, returning (scores [M, k], rows
+        [M, k], logits [M, pool]). The pool is the search of the other options
+        (``where``, ``expand``, ``boost``, ``lexical`` with ``query_terms``) at
+        ``k = pool`` with ``node_rows=True`` by whatever route that takes;
+        rows it marked -1 are empty slots. Every (query, memory) pair is read
+        as one sequence by the store's cross-encoder (ops/crossenc_ops.py
+        holds the contract): the classification logit is the score, nothing
+        of the first stage is blended in. The ``k`` largest logits come back
+        descending, ties to the lower row, (-inf, -1) once the pool's real
+        rows ran out; ``logits`` in pool order, -inf in empty slots.
+        ``query_tokens``: the queries' texts, or ``(ids [M, <= 64], lens)``.
+        Building or extending the token column is host work; beyond it the
+        only host synchronisation is one 8-byte read-back per chunk of
+        queries (the packed token count and the longest sequence, which size
+        the forward)."""
+        from ..core.search_spec import SearchSpec
+        if rerank is None or rerank is False:
+            raise ValueError("rerank settings are required")
+        spec = SearchSpec.of(k, where, expand=expand, boost=boost, lexical=lexical, rerank=rerank)
+        if self.reranker is None:
+            raise ValueError("rerank= needs a store with a reranker (HBMStore(reranker=...))")
+        if query_tokens is None:
+            raise ValueError("a re-ranked search needs the queries' text: pass query_tokens=")
+        if spec.lexical is not None and query_terms is None:
+            raise ValueError("a lexical search needs the queries' text: pass query_terms=")
+        return self._store_search_rerank(Q, int(k), metric, spec, query_terms, query_tokens)
+
+    def _store_search_rerank(self, Q, k, metric, spec, query_terms, query_tokens):
+        from ..ops.crossenc_ops import as_query_tokens
+        ce = self.reranker
+        P = spec.rerank.pool
+        M = 1 if Q.dim() == 1 else Q.shape[0]
+        qtok, qlen = as_query_tokens(query_tokens, ce.tokenizer)
+        if qtok.shape[0] != M:
+            raise ValueError(f"{M} queries but the tokens of {qtok.shape[0]}")
+        _, pool = self._search(Q, P, metric, True, spec.only("where", "expand", "boost", "lexical"), query_terms)
+        self.reranked_searches += 1
+        self.rerank_pairs += M * P
+        _, nothing = self._queries(Q)
+        if nothing or M == 0:  # (all padding)
+            s, r = self._no_hits(M, k)
+            return s, r, torch.full((M, P), NEG_INF, device=self.device)
+        col = self.token_column()
+        n = self.n
+        with self.on_stream():
+            return ce.rerank(pool, qtok, qlen, col.tok, col.dlen, k, col.L, n)
+
     # ---- multi-query search
     fused_searches = fused_groups = 0
 
     def store_search_fused(self, Q, offsets, k, metric: str = "l2", fuse="rrf", where=None, expand=None, boost=None,
-                           lexical=None, query_terms=None, weights=None):
+                           lexical=None, query_terms=None, weights=None, rerank=None):
         """One ranked list per GROUP of sub-queries: ``offsets`` (``NG + 1``
         ascending entries from 0 to ``M``, on the host) cuts the ``M`` rows of
         ``Q`` into groups of 1 .. 16. Every sub-query's pool is the search of
@@ -2738,6 +2827,8 @@ class TenantGraph:
         from ..core.fuse import QueryFusion
         from ..core.search_spec import SearchSpec
         from ..ops.fuse_ops import fuse_select, group_sizes
+        if rerank is not None and rerank is not False:
+            raise NotImplementedError("a fused search does not take rerank=: re-rank each query's own search")
         fu = QueryFusion.coerce(fuse)
         if fu is None:
             raise ValueError("fuse settings are required")
@@ -2767,10 +2858,10 @@ class TenantGraph:
         return scores, rows, support
 
     def search_ids_fused(self, Q, offsets, k, metric: str = "l2", fuse="rrf", where=None, expand=None, boost=None,
-                         lexical=None, query_terms=None, weights=None) -> List[List[str]]:
+                         lexical=None, query_terms=None, weights=None, rerank=None) -> List[List[str]]:
         """:meth:`store_search_fused`, one id list per group."""
         _, r, _ = self.store_search_fused(Q, offsets, k, metric, fuse, where, expand, boost, lexical, query_terms,
-                                          weights)
+                                          weights, rerank)
         ids = self.ids
         return [[ids[x] for x in row if x >= 0] for row in r.cpu().tolist()]
 
@@ -3287,15 +3378,17 @@ class TenantGraph:
         return s, self._nodes_only(r) if node_rows else r  # (the kernel above marks them itself)
 
     def search_ids(self, Q, k: int, metric: str = "l2", where=None, diversity=None, fetch_k=None,
-                   expand=None, boost=None, lexical=None, query_terms=None) -> List[List[str]]:
+                   expand=None, boost=None, lexical=None, query_terms=None, rerank=None,
+                   query_tokens=None) -> List[List[str]]:
         from ..core.search_spec import SearchSpec
-        return self._search_ids(Q, int(k), metric, SearchSpec.of(k, where, diversity, fetch_k, expand, boost, lexical),
-                                query_terms)
+        return self._search_ids(Q, int(k), metric,
+                                SearchSpec.of(k, where, diversity, fetch_k, expand, boost, lexical, rerank),
+                                query_terms, query_tokens)
 
-    def _search_ids(self, Q, k, metric, spec, query_terms=None) -> List[List[str]]:
+    def _search_ids(self, Q, k, metric, spec, query_terms=None, query_tokens=None) -> List[List[str]]:
         # (with an option, node rows only: a row the caller would drop must not take a pick; the plain
         # search returns the store's rows, ghosts included, and the caller drops them)
-        _, r = self._search(Q, k, metric, spec is not None, spec, query_terms)
+        _, r = self._search(Q, k, metric, spec is not None, spec, query_terms, query_tokens)
         ids = self.ids
         return [[ids[x] for x in row if x >= 0] for row in r.cpu().tolist()]
 

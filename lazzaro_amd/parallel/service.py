@@ -694,19 +694,20 @@ class DistributedMemoryService:
 
     # ------------------------------------------------------------ columnar search (routing.py)
     def search_routed(self, users: Sequence[str], queries, limit=5, where=None, diversity=None,
-                      fetch_k=None, expand=None, boost=None, lexical=None) -> "routing.RoutedHits":
+                      fetch_k=None, expand=None, boost=None, lexical=None, rerank=None) -> "routing.RoutedHits":
         """SPMD batched search_memories with tensors on the wire: ``queries``
         are texts (embedded here, by this rank's replica of the encoder) or an
         embedding tensor [n, D]; each goes to ``users[q]``'s owner in one
         all-to-all and its (score, row) hits come back in one more. Returns a
         :class:`~.routing.RoutedHits` in the caller's order."""
         SearchSpec.refuse("DistributedMemoryService.search_routed", where=where, diversity=diversity, fetch_k=fetch_k,
-                          expand=expand, boost=boost, lexical=lexical)
+                          expand=expand, boost=boost, lexical=lexical,
+                          rerank=rerank or None)
         Q = self._embed_front(queries)
         return routing.search_routed(self, list(users), Q, limit)
 
     def search_routed_stream(self, batches, limit=5, where=None, diversity=None, fetch_k=None, expand=None,
-                             boost=None, lexical=None):
+                             boost=None, lexical=None, rerank=None):
         """Pipelined :meth:`search_routed` for serving loops (the routed
         counterpart of ``MemorySystem.search_memories_stream``): ``batches``
         yields (users, query texts); batch i+1's front-end embed is enqueued
@@ -715,7 +716,8 @@ class DistributedMemoryService:
         under the search instead of after it. Every rank must iterate alike.
         Yields one :class:`~.routing.RoutedHits` per batch, in order."""
         SearchSpec.refuse("DistributedMemoryService.search_routed_stream", where=where, diversity=diversity,
-                          fetch_k=fetch_k, expand=expand, boost=boost, lexical=lexical)
+                          fetch_k=fetch_k, expand=expand, boost=boost, lexical=lexical,
+                          rerank=rerank or None)
         dev = self.comm.device
         side = None
         if dev.type == "cuda":
@@ -748,11 +750,12 @@ class DistributedMemoryService:
             cur, q_cur = nxt, q_nxt
 
     def search_global_batch(self, queries, limit: int = 5, where=None, diversity=None,
-                            fetch_k=None, expand=None, boost=None, lexical=None) -> "routing.GlobalHits":
+                            fetch_k=None, expand=None, boost=None, lexical=None, rerank=None) -> "routing.GlobalHits":
         """SPMD: this rank's queries against every resident tenant of every
         rank (all-gather of queries, local search, one all-to-all back)."""
         SearchSpec.refuse("DistributedMemoryService.search_global_batch", where=where, diversity=diversity,
-                          fetch_k=fetch_k, expand=expand, boost=boost, lexical=lexical)
+                          fetch_k=fetch_k, expand=expand, boost=boost, lexical=lexical,
+                          rerank=rerank or None)
         return routing.search_global_batch(self, self._embed_front(queries), limit)
 
     def resolve(self, hits: "routing.RoutedHits") -> List[List[Dict]]:
@@ -791,12 +794,13 @@ class DistributedMemoryService:
 
     # ------------------------------------------------------------ global search (C1 + K2)
     def search_global(self, query_emb: torch.Tensor, limit: int = 5, metric: str = "l2", where=None, diversity=None,
-                      fetch_k=None, expand=None, boost=None, lexical=None) -> List[Dict]:
+                      fetch_k=None, expand=None, boost=None, lexical=None, rerank=None) -> List[Dict]:
         """Top-``limit`` over every resident tenant of every rank for one
         query vector (exact store scores: -|q-x|^2 for L2). Returns the same
         list of {user_id, node...} dicts on every rank."""
         SearchSpec.refuse("DistributedMemoryService.search_global", where=where, diversity=diversity, fetch_k=fetch_k,
-                          expand=expand, boost=boost, lexical=lexical)
+                          expand=expand, boost=boost, lexical=lexical,
+                          rerank=rerank or None)
         comm = self.comm
         cands = []
         for user, ms in self.systems.items():

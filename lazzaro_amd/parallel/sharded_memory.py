@@ -574,7 +574,7 @@ class ShardedMemorySystem:
         return out
 
     def search_memories_batch(self, queries: Sequence[str], limit: int = 5, where=None, diversity=None,
-                              fetch_k=None, expand=None, boost=None, lexical=None) -> List[List[Dict]]:
+                              fetch_k=None, expand=None, boost=None, lexical=None, rerank=None) -> List[List[Dict]]:
         """Collective ``search_memories`` over the whole tenant (reference
         :1460-1472): every rank embeds its own queries, the query rows are
         all-gathered, each rank runs the store search (fused scan + fp32
@@ -582,7 +582,8 @@ class ShardedMemorySystem:
         (ties -> lower node number) and the winners' node dicts are returned
         to the rank that asked. Returns this rank's results."""
         SearchSpec.refuse("ShardedMemorySystem.search_memories_batch", where=where, diversity=diversity,
-                          fetch_k=fetch_k, expand=expand, boost=boost, lexical=lexical)
+                          fetch_k=fetch_k, expand=expand, boost=boost, lexical=lexical,
+                          rerank=rerank or None)
         g = self.g
         dev = self.device
         qs = list(queries)
