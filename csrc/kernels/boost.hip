@@ -17,6 +17,7 @@
 // view one element into a buffer takes the 4-byte path), a capped grid strides
 // over the row groups, and the last n % 4 rows go row by row.
 #include "lzk_common.h"
+#include "lzk_rowpred.h"
 
 namespace {
 
@@ -28,21 +29,7 @@ struct BoostTable {
   double w[256];  // weight per type code (by value: 2 KiB of kernel arguments, staged into LDS)
 };
 
-struct BoostArgs {
-  double w_sal, w_freq, w_rec, scale, now, c;
-};
-
-__device__ __forceinline__ float boost_row(float base, float sal, int acc, double t, unsigned kind, double tw,
-                                           const BoostArgs& a) {
-#pragma clang fp contract(off)
-  const double f = fmin(1.0, (double)acc / 10.0);
-  const double age = fmax(0.0, a.now - t);
-  const double rec = 1.0 / (1.0 + age / a.scale);
-  const double B = ((a.w_sal * (double)sal + a.w_freq * f) + a.w_rec * rec) + tw;
-  float p = (float)(a.c * B);
-  if (!(fabsf(p) <= 3.402823466e+38f)) p = 0.0f;  // NaN or inf (a NaN salience, an fp32 overflow): no prior
-  return kind == 1u ? base + p : LZK_NEG_INF;  // (a select, not a branch: the 16-byte loads stay whole)
-}
+// BoostArgs and boost_row: lzk_rowpred.h
 
 template <bool VEC, bool TYPES>
 __global__ __launch_bounds__(NTB) void boost_bias_kernel(const float* __restrict__ base, const float* __restrict__ sal,

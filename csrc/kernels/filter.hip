@@ -25,6 +25,7 @@
 // entries that beat the query's running list (kept sorted across lanes 0..K-1)
 // -- usually none after the first slabs, so the pass costs one wave argmax.
 #include "lzk_common.h"
+#include "lzk_rowpred.h"
 
 LZK_DEBUG_STATE(filter)
 
@@ -32,73 +33,7 @@ namespace {
 
 constexpr int FP_NT = 256;
 
-}  // namespace
-
-// by-value scalar bounds of the predicate (ops/filter_ops.py FilterBounds)
-struct LzkFilterBounds {
-  double since, until, accessed_since;
-  float min_sal, max_sal;
-  int min_acc;
-  int sup_mode;        // -1 both, 0 no super-nodes, 1 only super-nodes
-  int flags;           // FB_* bits: which tests apply
-  int n_shard_bits;    // shard codes covered by the shard bitmap
-  int neg_shard_pass;  // rows with shard code < 0 (the default shard's label) pass the shard test
-  int l2;              // bias of a passing row: 0 - sqn (1) or 0 (0)
-  unsigned type_mask[8];  // 256 bits over type codes
-};
-
-namespace {
-
-enum {
-  FB_TYPES = 1, FB_SHARDS = 2, FB_MIN_SAL = 4, FB_MAX_SAL = 8, FB_SINCE = 16, FB_UNTIL = 32,
-  FB_ACC_SINCE = 64, FB_MIN_ACC = 128, FB_EXCLUDE = 256
-};
-
-struct FilterCols {
-  const float* sal;
-  const int* acc;
-  const double* last;
-  const double* ts;
-  const int* shard;
-  const uint8_t* kind;
-  const uint8_t* sup;
-  const uint8_t* stored;
-  const uint8_t* tcode;          // type codes (FB_TYPES)
-  const unsigned* shard_bits;    // bitmap over shard codes (FB_SHARDS)
-  const unsigned* exclude_bits;  // bitmap over rows (FB_EXCLUDE)
-};
-
-__device__ __forceinline__ bool fp_pass(const FilterCols& c, const LzkFilterBounds& b, long i) {
-  if (c.kind[i] != 1 || c.stored[i] != 1) return false;  // memories only: NODE rows in the store
-  const int f = b.flags;
-  if (b.sup_mode >= 0 && (int)(c.sup[i] != 0) != b.sup_mode) return false;
-  if (f & FB_TYPES) {
-    const unsigned t = c.tcode[i];
-    if (!((b.type_mask[t >> 5] >> (t & 31)) & 1u)) return false;
-  }
-  if (f & FB_SHARDS) {
-    const int s = c.shard[i];
-    if (s < 0) {
-      if (!b.neg_shard_pass) return false;
-    } else if (s >= b.n_shard_bits || !((c.shard_bits[s >> 5] >> (s & 31)) & 1u)) {
-      return false;
-    }
-  }
-  if (f & (FB_MIN_SAL | FB_MAX_SAL)) {
-    const float s = c.sal[i];
-    if ((f & FB_MIN_SAL) && !(s >= b.min_sal)) return false;
-    if ((f & FB_MAX_SAL) && !(s <= b.max_sal)) return false;
-  }
-  if (f & (FB_SINCE | FB_UNTIL)) {
-    const double t = c.ts[i];
-    if ((f & FB_SINCE) && !(t >= b.since)) return false;
-    if ((f & FB_UNTIL) && !(t < b.until)) return false;
-  }
-  if ((f & FB_ACC_SINCE) && !(c.last[i] >= b.accessed_since)) return false;
-  if ((f & FB_MIN_ACC) && !(c.acc[i] >= b.min_acc)) return false;
-  if ((f & FB_EXCLUDE) && ((c.exclude_bits[i >> 5] >> (i & 31)) & 1u)) return false;
-  return true;
-}
+// LzkFilterBounds (ops/filter_ops.py FilterBounds), FilterCols and fp_pass: lzk_rowpred.h
 
 // pass 1: bias[i] and the number of passing rows of every 256-row block
 __global__ __launch_bounds__(FP_NT) void fp_eval_kernel(FilterCols c, LzkFilterBounds b, const float* __restrict__ sqn,

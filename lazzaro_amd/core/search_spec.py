@@ -77,6 +77,20 @@ class SearchSpec:
         kw = {f.name: v for f, v in ((f, getattr(self, f.name)) for f in fields(self)) if v is not None}
         return dict(kw, **texts) if self.needs_text else kw
 
+    def as_dict(self) -> Dict[str, Any]:
+        """The options that are set in a JSON-able normal form (what a served
+        request carries between ranks): every settings record as the dict of
+        its fields, sets as sorted lists. ``SearchSpec.of(limit,
+        **json.loads(json.dumps(spec.as_dict())))`` is an equal spec."""
+        return {name: (v.to_dict() if hasattr(v, "to_dict") else v) for name, v in self.kwargs().items()}
+
+    @property
+    def bias_only(self) -> bool:
+        """Only ``where`` and / or ``boost`` are set: the search is the plain
+        scan under another bias column (ops/mt_bias_ops.py)."""
+        return (self.diversity is None and self.fetch_k is None and self.expand is None and self.lexical is None
+                and self.rerank is None)
+
     def only(self, *names: str) -> Optional["SearchSpec"]:
         """The spec of an inner search that keeps the options ``names``."""
         kept = {name: getattr(self, name) for name in names}

@@ -3045,6 +3045,38 @@ class TenantGraph:
             cache.popitem(last=False)
         return plan
 
+    def _mt_bias_job(self, flt=None, boost=None, metric: str = "l2"):
+        """This tenant's job of a served round (ops.mt_bias_ops.MtBiasJob):
+        the columns, the filter resolved against this tenant (type and shard
+        names to codes, excluded ids to rows) and the boost's type-weight
+        table by this tenant's codes, as :meth:`_boost_plan` builds it.
+        ``flt``: a MemoryFilter or None; ``boost``: a MemoryBoost with ``now``
+        set, or None. The column ``mt_bias`` writes for the job is, bit for
+        bit, ``_filter_plan(flt, l2).bias`` / ``boost_bias(boost, metric,
+        where=flt)``. Call it under the graph lock: the addresses it takes
+        (the type-code column's among them) must not move before the launch
+        that reads them is enqueued. Builds no plan, caches nothing, reads
+        nothing back."""
+        from ..ops.boost_ops import metric_scale
+        from ..ops.filter_ops import PLAN_COLS
+        from ..ops.mt_bias_ops import MtBiasJob
+        l2 = metric == "l2"
+        need_codes = (flt is not None and flt.types is not None) or (boost is not None and bool(boost.type_weights))
+        if need_codes:
+            self._type_codes()
+        pred = None if flt is None else self._resolve_filter(flt)
+        tw = None
+        if boost is not None and boost.type_weights:
+            tw = [0.0] * 256
+            for name, w in boost.type_weights.items():
+                code = self.type_code.get(name)
+                if code is not None:  # a type the tenant never saw adds nothing
+                    tw[code] = w
+        return MtBiasJob({c: getattr(self, c) for c in PLAN_COLS}, self.n, pred, l2,
+                         self.sqn if (pred is not None and l2) else None,
+                         self.store_bias("l2" if l2 else "ip") if pred is None else None,
+                         self._tcode if need_codes else None, boost, tw, metric_scale(metric))
+
     def _store_search_where(self, Q, k, metric, where, boost=None):
         """:meth:`store_search` restricted to the rows passing ``where``.
         Routes: no passing row -> all -1, no scan; on the GPU (L2, IP,

@@ -27,6 +27,7 @@ All collective methods must be called by every rank in the same order.
 """
 from __future__ import annotations
 
+import dataclasses
 import inspect
 import os
 import weakref
@@ -169,6 +170,15 @@ class DistributedMemoryService:
         self._membership = 0  # bumps whenever a tenant becomes / stops being resident
         self.route_stats = {"device": 0, "host": 0}  # routed batches served by device key matching / by name
         self._owner_epoch: Dict[int, int] = {}
+        # options in the served batch (see serve): requests that carried options, bias columns built for
+        # them on the fused path (one per distinct (tenant, filter, boost) of a round), requests with
+        # options answered per tenant instead
+        self.mt_stats = {"mt_option_requests": 0, "mt_bias_jobs": 0, "mt_option_fallbacks": 0}
+
+    def stats(self) -> Dict[str, int]:
+        """Counters of this rank's serving paths: the routed batches by route
+        (``route_stats``) and the option counters of :meth:`serve`."""
+        return {**{"routed_" + k: v for k, v in self.route_stats.items()}, **self.mt_stats}
 
     # ------------------------------------------------------------ placement
     def owner(self, user: str) -> int:
@@ -517,7 +527,21 @@ class DistributedMemoryService:
         request (Nodes as dicts); a ``search_memories`` result served by the
         fused GPU path is a :class:`SearchHits` sequence of those dicts, built
         when first read (``list(r)`` for a plain list, e.g. before
-        ``json.dumps``)."""
+        ``json.dumps``).
+
+        A ``search_memories`` request may carry a third argument, a dict of
+        search options: ``(user, "search_memories", query, limit, {"where":
+        {...}, "boost": 0.5})`` -- any option ``MemorySystem.search_memories``
+        takes, one setting per REQUEST. The dict is validated here, before the
+        exchange (``SearchSpec.of``: an unknown key or a bad value raises
+        ``ValueError`` on the sender; a boost's ``now`` is read once per
+        call), and crosses ranks as ``SearchSpec.as_dict()``. Results are
+        those of the tenant's own search with the options. ``where`` and
+        ``boost`` ride the fused batch: the owner builds one bias column per
+        distinct (tenant, filter, boost) of the round in one launch
+        (ops/mt_bias_ops.py) and points those queries' bias addresses at it;
+        a request with any other option is answered by its tenant's
+        ``search_memories_batch`` (``stats()["mt_option_fallbacks"]``)."""
         return self._serve_finish(self._serve_submit(requests))
 
     def serve_stream(self, rounds: Iterable[Sequence[Tuple]]):
@@ -543,11 +567,15 @@ class DistributedMemoryService:
         rows it gathered are mapped to nodes before they can move."""
         comm = self.comm
         out_req: List[List] = [[] for _ in range(comm.world)]
+        clock: List[float] = []  # the round's ``now``, read once, when the first boost without one asks
         for i, req in enumerate(requests):
             user, method = req[0], req[1]
             if method not in ALLOWED:
                 raise ValueError(f"method {method!r} is not served")
-            out_req[self.owner(user)].append([i, user, method, list(req[2:])])
+            args = list(req[2:])
+            if method == "search_memories" and len(args) > 2:
+                args[2:] = self._wire_options(args, clock)
+            out_req[self.owner(user)].append([i, user, method, args])
         inbox = self._exchange(out_req)
         replies: List[List] = [[] for _ in range(comm.world)]
         # searches of every source and tenant run as one batch (one embed,
@@ -563,7 +591,10 @@ class DistributedMemoryService:
         for src, items in enumerate(inbox):
             for i, user, method, args in items:
                 if method == "search_memories":
-                    pending.append((src, i, user, args[0], int(args[1]) if len(args) > 1 else 5))
+                    limit = int(args[1]) if len(args) > 1 else 5
+                    # (the owner rebuilds the spec from its normal form: idempotent, reads no clock)
+                    spec = SearchSpec.of(limit, **args[2]) if len(args) > 2 else None
+                    pending.append((src, i, user, args[0], limit, spec))
                     continue
                 if any(p[2] == user for p in pending):
                     flush()
@@ -574,6 +605,38 @@ class DistributedMemoryService:
                 replies[src].append([i, _jsonable(getattr(self.system(user), method)(*args))])
         handle = self._search_submit(pending) if pending else None
         return [len(requests), replies, list(pending), handle]
+
+    @staticmethod
+    def _wire_options(args: List, clock: List[float]) -> List:
+        """The options dict of a ``search_memories`` request (``args`` = query,
+        limit, options) validated and in its JSON-able normal form: ``[]`` for
+        no options, else ``[SearchSpec.as_dict()]``."""
+        from ..core import boost as _boost
+        if len(args) > 3:
+            raise ValueError("a search_memories request takes (query, limit, options): "
+                             f"{len(args) - 3} argument(s) too many")
+        options = args[2]
+        if options is None:
+            return []
+        if not isinstance(options, dict):
+            raise ValueError(f"the options of a search_memories request must be a dict, not {type(options).__name__}")
+        known = tuple(f.name for f in dataclasses.fields(SearchSpec))
+        bad = sorted(str(k) for k in options if k not in known)
+        if bad:
+            raise ValueError(f"unknown search option(s): {', '.join(bad)} (known: {', '.join(known)})")
+        opts = dict(options)
+        try:
+            if opts.get("boost") is not None:
+                b = _boost.MemoryBoost.coerce(opts["boost"])
+                if b.now is None:
+                    if not clock:
+                        clock.append(float(_boost._clock()))
+                    b = b.at(clock[0])
+                opts["boost"] = b
+            spec = SearchSpec.of(args[1], **opts)
+        except TypeError as e:
+            raise ValueError(str(e)) from e
+        return [] if spec is None else [spec.as_dict()]
 
     def _serve_finish(self, state) -> List:
         n, replies, pending, handle = state
@@ -600,7 +663,11 @@ class DistributedMemoryService:
         L2 of the reference's store search), then one pointer-table gather of
         the result rows' fields, copied to pinned memory asynchronously: the
         returned handle is finished by :meth:`_search_finish` (which holds
-        the tenants' graph locks until then). Otherwise per tenant, at once."""
+        the tenants' graph locks until then). Otherwise per tenant, at once.
+        A request may carry a sixth element, its ``SearchSpec``: on the fused
+        path one that holds only ``where`` / ``boost`` scans under its own
+        bias column (:meth:`_option_bias`), any other is answered by its
+        tenant's own search at once; off it every one is."""
         users = [p[2] for p in pending]
         systems = {u: self.system(u) for u in dict.fromkeys(users)}
         first = next(iter(systems.values()))
@@ -610,16 +677,33 @@ class DistributedMemoryService:
                  and max(p[4] for p in pending) <= 16
                  and all(ms.embedder is emb0 and getattr(ms.store, "metric", "l2") == "l2"
                          and ms._store_binds_graph() for ms in systems.values()))
+        opt = 0
+        for p in pending:
+            if len(p) > 5 and p[5] is not None:
+                opt += 1
+        if opt == 0 and fused:  # a round without options: nothing below applies to it
+            slow_none = True
+        else:
+            slow_none = False
+            pending = [p if len(p) > 5 else tuple(p) + (None,) for p in pending]  # (.., spec): None = no options
+        self.mt_stats["mt_option_requests"] += opt
         if not fused:
-            out, j = [], 0
-            while j < len(pending):  # consecutive same-tenant, same-limit runs batch
-                k = j
-                while k < len(pending) and pending[k][2] == pending[j][2] and pending[k][4] == pending[j][4]:
-                    k += 1
-                res = systems[pending[j][2]].search_memories_batch([p[3] for p in pending[j:k]], limit=pending[j][4])
-                out += [[node_dict(n) for n in r] for r in res]
-                j = k
-            return ("done", out)
+            self.mt_stats["mt_option_fallbacks"] += opt
+            return ("done", self._search_per_tenant(systems, pending))
+        # a request with an option beyond where / boost is answered by its tenant's own search
+        whole = pending
+        slow = [] if slow_none else [q for q, p in enumerate(whole) if p[5] is not None and not p[5].bias_only]
+        merge = None
+        if slow:
+            self.mt_stats["mt_option_fallbacks"] += len(slow)
+            gone = set(slow)
+            fast = [q for q in range(len(whole)) if q not in gone]
+            slow_res = self._search_per_tenant(systems, [whole[q] for q in slow])
+            if not fast:
+                return ("done", slow_res)
+            merge = (len(whole), fast, slow, slow_res)
+            pending = [whole[q] for q in fast]
+            users = [p[2] for p in pending]
         from ..ops.search import segment_topk_ptrs
         from ..ops.tenant_ops import gather_fields
         from ..utils.tracing import tracer
@@ -643,11 +727,15 @@ class DistributedMemoryService:
                 if wrong:
                     nrows = nrows.clone()
                     nrows[torch.as_tensor(wrong, device=dev)] = 0
+                bptr = ptrs[1].contiguous()
+                keep_opt: list = []
+                if not slow_none and any(p[5] is not None for p in pending):
+                    bptr = self._option_bias(pending, graphs, D, bptr, keep_opt)
             qb = -(Q * Q).sum(1)
             k = max(p[4] for p in pending)
             with tracer.stage("mt_scan", first._device):
                 _, rows = segment_topk_ptrs(ptrs[0].contiguous(), nrows.contiguous(), D, Q.contiguous(), k,
-                                            bptr=ptrs[1].contiguous(), alpha=2.0, qbias=qb)
+                                            bptr=bptr, alpha=2.0, qbias=qb)
             # the result rows' fields in one gather over the per-query column
             # pointers of the tenant table (the tenants' columns are separate
             # allocations)
@@ -659,17 +747,75 @@ class DistributedMemoryService:
                 host[n].copy_(t, non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
-            return ("fused", pending, qg, host, ev, locks, (Q, ptrs, nrows, f))
+            return ("fused", pending, qg, host, ev, locks, (Q, ptrs, nrows, f, bptr, keep_opt), merge)
         except BaseException:
             for lk in reversed(locks):
                 lk.release()
             raise
 
+    def _search_per_tenant(self, systems, pending: List[Tuple]) -> List[List[Dict]]:
+        """Each request through its tenant's ``search_memories_batch``:
+        consecutive same-tenant, same-limit requests without options batch; a
+        request with options runs alone, with them."""
+        out, j = [], 0
+        while j < len(pending):
+            k = j + 1
+            spec = pending[j][5]
+            if spec is None:
+                while k < len(pending) and pending[k][2] == pending[j][2] and pending[k][4] == pending[j][4] \
+                        and pending[k][5] is None:
+                    k += 1
+            res = systems[pending[j][2]].search_memories_batch([p[3] for p in pending[j:k]], limit=pending[j][4],
+                                                               **({} if spec is None else spec.kwargs()))
+            out += [[node_dict(n) for n in r] for r in res]
+            j = k
+        return out
+
+    def _option_bias(self, pending: List[Tuple], graphs, D: int, bptr: torch.Tensor, keep: list) -> torch.Tensor:
+        """The bias addresses of a fused round whose requests carry ``where``
+        / ``boost``: one column per distinct (tenant, filter, boost) written
+        by ONE ``mt_bias`` launch, and ``bptr`` with those queries pointed at
+        their column (the others keep the tenant table's store bias). Under
+        the graphs' locks, on the current stream, no host synchronisation."""
+        from ..ops.mt_bias_ops import mt_bias
+        index: Dict[Tuple, int] = {}
+        jobs, qjob = [], []
+        for p in pending:
+            spec, g = p[5], graphs[p[2]]
+            if spec is None or g.dim != D or g.n == 0 or g.emb32 is None:  # (no rows to score: nothing to mask)
+                qjob.append(-1)
+                continue
+            key = (p[2], None if spec.where is None else spec.where.key(),
+                   None if spec.boost is None else spec.boost.key())
+            j = index.get(key)
+            if j is None:
+                j = index[key] = len(jobs)
+                jobs.append(g._mt_bias_job(spec.where, spec.boost, "l2"))
+            qjob.append(j)
+        if not jobs:
+            return bptr
+        self.mt_stats["mt_bias_jobs"] += len(jobs)
+        arena, offs = mt_bias(jobs, keep)
+        base = arena.data_ptr()
+        addr = np.asarray([base + 4 * offs[j] if j >= 0 else 0 for j in qjob], np.int64)
+        over = routing._to_dev(torch.from_numpy(addr), bptr.device)
+        keep += [arena, over]
+        return torch.where(over != 0, over, bptr).contiguous()
+
     def _search_finish(self, h) -> List[List[Dict]]:
         if h[0] == "done":
             return h[1]
         from ..utils.tracing import tracer
-        _, pending, qg, host, ev, locks, _keep = h
+        _, pending, qg, host, ev, locks, _keep, merge = h
+        if merge is not None:  # the fused requests' results among those answered per tenant
+            n, fast, slow, slow_res = merge
+            res = self._search_finish(h[:7] + (None,))
+            out: List = [None] * n
+            for q, r in zip(fast, res):
+                out[q] = r
+            for q, r in zip(slow, slow_res):
+                out[q] = r
+            return out
         try:
             ev.synchronize()
             with tracer.stage("mt_results", "cpu"):
