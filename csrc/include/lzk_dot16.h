@@ -1,5 +1,7 @@
 // The 16-lanes-per-row dot product shared by the selection kernels that score
-// gathered fp32 rows against a vector held in LDS (mmr.hip, expand.hip).
+// gathered fp32 rows against a vector held in LDS (mmr.hip, expand.hip,
+// lexical.hip's fusion, fuse.hip's mean mode) and, for the fold alone, by
+// crossenc.hip's head, which keeps this lane-to-dimension map over bf16 rows.
 //
 // Lane `part` (0 .. 15) of a group takes a FIXED share of the dimensions,
 // whichever slot, group or wave the row sits in -- d4 == part (mod 16) over
@@ -34,6 +36,20 @@ __device__ __forceinline__ void lzk_dot16_part(const float* a, const float* __re
       xx = fmaf(xv, xv, xx);
     }
   }
+}
+
+// this lane's share of |a|^2 in the same order (a: LDS, zero padded to a multiple of 4): the query's norm
+__device__ __forceinline__ float lzk_sq16_part(const float* a, int D, int vec, int part) {
+  float aa = 0.f;
+  if (vec) {
+    for (int d4 = part; d4 < (D >> 2); d4 += 16) {
+      const float4 v = *reinterpret_cast<const float4*>(a + 4 * d4);
+      aa = fmaf(v.x, v.x, aa); aa = fmaf(v.y, v.y, aa); aa = fmaf(v.z, v.z, aa); aa = fmaf(v.w, v.w, aa);
+    }
+  } else {
+    for (int d = part; d < D; d += 16) aa = fmaf(a[d], a[d], aa);
+  }
+  return aa;
 }
 
 // the 16 partial sums of a group, in the one fixed order

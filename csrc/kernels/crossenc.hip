@@ -27,9 +27,9 @@
 //            output, tanhf per element, the dot in lzk_dot16.h's order (lane
 //            `part` takes the float4 indices d4 == part mod 16 ascending, one
 //            fmaf each, folded by xor 8, 4, 2, 1); empty slots get -inf. The
-//            slots' 64-bit (logit, row) keys are sorted by one wave (this
-//            file's own copy of widek.hip's helpers; a pool is one 64-entry
-//            block, so the tournament has no merge round) and the k largest
+//            slots' 64-bit (logit, row) keys are sorted by one wave
+//            (lzk_topk64.h's wave_sort_desc; a pool is one 64-entry block,
+//            so the tournament has no merge round) and the k largest
 //            come back descending, ties to the lower row, (-inf, -1) beyond
 //            the pool's real rows.
 //
@@ -46,10 +46,9 @@
 // The CPU tier sums in another order; the bound holds for every order.
 #include "lzk_common.h"
 #include "lzk_dot16.h"
+#include "lzk_topk64.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int CE_MAX_Q = 64;      // query tokens kept (MAX_QUERY_TOKENS)
 constexpr int CE_MAX_L = 128;     // memory tokens kept, at most
@@ -201,39 +200,6 @@ __global__ __launch_bounds__(256) void ce_embed_ln_kernel(
       }
     }
   }
-}
-
-__device__ __forceinline__ u64 wide_key(float s, int row) {
-  if (!(s == s)) s = LZK_NEG_INF;
-  s += 0.0f;  // -0 -> +0: the order treats them as equal
-  const unsigned u = __float_as_uint(s);
-  const unsigned m = (u >> 31) ? ~u : (u | 0x80000000u);
-  return ((u64)m << 32) | (u64)(0xffffffffu - (unsigned)row);
-}
-
-__device__ __forceinline__ void wide_unkey(u64 key, float& s, int& row) {
-  const unsigned m = (unsigned)(key >> 32);
-  const unsigned u = (m >> 31) ? (m & 0x7fffffffu) : ~m;
-  s = __uint_as_float(u);
-  row = (int)(0xffffffffu - (unsigned)(key & 0xffffffffu));
-  if (m == 0u || s == LZK_NEG_INF) { s = LZK_NEG_INF; row = -1; }
-}
-
-__device__ __forceinline__ u64 kmax(u64 a, u64 b) { return a > b ? a : b; }
-__device__ __forceinline__ u64 kmin(u64 a, u64 b) { return a < b ? a : b; }
-
-// 64 keys, one per lane -> descending by lane.
-__device__ __forceinline__ u64 wave_sort_desc(u64 v, int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const u64 o = __shfl_xor(v, j, 64);
-      const bool low = (lane & j) == 0, desc = (lane & k) == 0;
-      v = (low == desc) ? kmax(v, o) : kmin(v, o);
-    }
-  }
-  return v;
 }
 
 // X: the pooler's dense output before its tanh, bf16 [M * P, H] with row stride ldx

@@ -21,7 +21,7 @@
 // read; a seed listed twice is one entry.
 //
 // Layout. EXP_NT = 256 threads. The query sits in LDS. The candidate table is
-// an open-addressing hash of EXP_HASH = 2048 slots (linear probing, at most
+// lzk_rowset.h's: an open-addressing hash of EXP_HASH = 2048 slots (at most
 // EXP_MAX_POOL = 1024 keys: the launcher refuses seeds * (1 + fanout)^hops
 // above that, so it never fills) keyed by the row; the rows are also appended
 // to a dense list in arrival order, which is what the passes iterate. Every
@@ -52,6 +52,7 @@
 // Identical rows get identical cosines, so equal activations give equal bits.
 #include "lzk_common.h"
 #include "lzk_dot16.h"
+#include "lzk_rowset.h"
 
 namespace {
 
@@ -67,26 +68,10 @@ __device__ __forceinline__ unsigned long long exp_pack(float act, unsigned rank)
   return ((unsigned long long)__float_as_uint(act) << 32) | rank;
 }
 
-// the slot of `row`, inserted if it is new (appended to the dense list then)
+// the slot of `row`, inserted if it is new (appended to the dense list then, its slot beside it)
 __device__ __forceinline__ int exp_insert(int row, int* s_key, int* s_list, int* s_slot, int* s_cnt) {
-  unsigned h = ((unsigned)row * 2654435761u) >> 21;  // 11 bits
-  for (;;) {
-    const int k = s_key[h];
-    if (k == row) return (int)h;
-    if (k == -1) {
-      const int old = atomicCAS(&s_key[h], -1, row);
-      if (old == -1) {
-        const int i = atomicAdd(s_cnt, 1);
-        if (i < EXP_MAX_POOL) {  // (always: the launcher bounds the pool)
-          s_list[i] = row;
-          s_slot[i] = (int)h;
-        }
-        return (int)h;
-      }
-      if (old == row) return (int)h;
-    }
-    h = (h + 1) & (EXP_HASH - 1);
-  }
+  return lzk_rowset_insert<EXP_HASH, EXP_MAX_POOL>(row, s_key, s_list, s_cnt,  // (the launcher bounds the pool)
+                                                   [&](unsigned h, int i) { s_slot[i] = (int)h; });
 }
 
 __global__ __launch_bounds__(EXP_NT) void expand_select_kernel(
@@ -126,19 +111,7 @@ __global__ __launch_bounds__(EXP_NT) void expand_select_kernel(
   const int nseed = min(s_cnt, EXP_MAX_POOL);
 
   // ---- |q|: every group sums the same shares in the same order
-  float qn;
-  {
-    float qq = 0.f;
-    if (vec) {
-      for (int d4 = part; d4 < (D >> 2); d4 += 16) {
-        const float4 v = *reinterpret_cast<const float4*>(s_q + 4 * d4);
-        qq = fmaf(v.x, v.x, qq); qq = fmaf(v.y, v.y, qq); qq = fmaf(v.z, v.z, qq); qq = fmaf(v.w, v.w, qq);
-      }
-    } else {
-      for (int d = part; d < D; d += 16) qq = fmaf(s_q[d], s_q[d], qq);
-    }
-    qn = sqrtf(lzk_fold16(qq));
-  }
+  const float qn = sqrtf(lzk_fold16(lzk_sq16_part(s_q, D, vec, part)));
 
   // ---- seed cosines and activations (nseed <= 16: one row per group)
   {

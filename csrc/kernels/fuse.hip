@@ -17,8 +17,8 @@
 //   result     the k largest by the fp32 score, ties to the lower row,
 //              (-inf, -1, support 0) beyond the candidate count
 //
-// Layout. FUSE_NT = 256 threads. The candidate table is expand.hip's scheme:
-// an open-addressing hash of FUSE_HASH = 2048 slots (linear probing, at most
+// Layout. FUSE_NT = 256 threads. The candidate table is lzk_rowset.h's, as in
+// expand.hip: an open-addressing hash of FUSE_HASH = 2048 slots (at most
 // FUSE_MAX_CAND = 1024 keys, so it never fills) keyed by the row, and a dense
 // list of the rows in arrival order. s_idx maps a hash slot to the row's place
 // in the dense list. The ranks are a byte matrix [1024][16] over (place,
@@ -31,8 +31,8 @@
 // depend on the arrival order. (3) scores: rrf -- one thread per candidate
 // sums its row of the matrix in j order; mean -- 16 lanes per candidate gather
 // the row ONCE and dot it against every staged query. (4) 64-bit (score, row)
-// keys and the bitonic tournament of 64-entry blocks (this file's own copy of
-// widek.hip's helpers). The order of the dense list depends on arrival;
+// keys and the bitonic tournament of 64-entry blocks (lzk_topk64.h, every
+// block unsorted: b0 = 0). The order of the dense list depends on arrival;
 // nothing that is returned does: keys are totally ordered and support is
 // looked up by row.
 //
@@ -56,10 +56,10 @@
 // Identical rows get identical cosines, so equal scores give equal bits.
 #include "lzk_common.h"
 #include "lzk_dot16.h"
+#include "lzk_rowset.h"
+#include "lzk_topk64.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int FUSE_NT = 256;
 constexpr int FUSE_MAX_Q = 16;       // sub-queries per group
@@ -68,103 +68,6 @@ constexpr int FUSE_MAX_CAND = 1024;  // FUSE_MAX_Q * FUSE_MAX_P: the union canno
 constexpr int FUSE_HASH = 2048;
 constexpr int FUSE_MAX_K = 64;
 constexpr int FUSE_MAX_QF = 16384;   // floats of staged queries: 64 KiB beside the 48 KiB of tables
-
-__device__ __forceinline__ u64 wide_key(float s, int row) {
-  if (!(s == s)) s = LZK_NEG_INF;
-  s += 0.0f;  // -0 -> +0: the order treats them as equal
-  const unsigned u = __float_as_uint(s);
-  const unsigned m = (u >> 31) ? ~u : (u | 0x80000000u);
-  return ((u64)m << 32) | (u64)(0xffffffffu - (unsigned)row);
-}
-
-__device__ __forceinline__ void wide_unkey(u64 key, float& s, int& row) {
-  const unsigned m = (unsigned)(key >> 32);
-  const unsigned u = (m >> 31) ? (m & 0x7fffffffu) : ~m;
-  s = __uint_as_float(u);
-  row = (int)(0xffffffffu - (unsigned)(key & 0xffffffffu));
-  if (m == 0u || s == LZK_NEG_INF) { s = LZK_NEG_INF; row = -1; }
-}
-
-__device__ __forceinline__ u64 kmax(u64 a, u64 b) { return a > b ? a : b; }
-__device__ __forceinline__ u64 kmin(u64 a, u64 b) { return a < b ? a : b; }
-
-// 64 keys, one per lane -> descending by lane.
-__device__ __forceinline__ u64 wave_sort_desc(u64 v, int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const u64 o = __shfl_xor(v, j, 64);
-      const bool low = (lane & j) == 0, desc = (lane & k) == 0;
-      v = (low == desc) ? kmax(v, o) : kmin(v, o);
-    }
-  }
-  return v;
-}
-
-// A bitonic sequence of 64 keys -> descending by lane.
-__device__ __forceinline__ u64 wave_merge_desc(u64 v, int lane) {
-#pragma unroll
-  for (int j = 32; j > 0; j >>= 1) {
-    const u64 o = __shfl_xor(v, j, 64);
-    v = (lane & j) == 0 ? kmax(v, o) : kmin(v, o);
-  }
-  return v;
-}
-
-// keys[0 .. 64 nb): every block unsorted. On return block 0 holds the 64 best
-// of all nb blocks, descending. Every thread of the block calls it (nb
-// block-uniform).
-__device__ __forceinline__ void topk64_rounds(u64* keys, int nb) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  for (int b = wave; b < nb; b += nw) keys[64 * b + lane] = wave_sort_desc(keys[64 * b + lane], lane);
-  for (int s = 1; s < nb; s <<= 1) {
-    __syncthreads();
-    for (int a = wave * 2 * s; a + s < nb; a += nw * 2 * s) {
-      const u64 A = keys[64 * a + lane];
-      const u64 B = keys[64 * (a + s) + 63 - lane];
-      keys[64 * a + lane] = wave_merge_desc(kmax(A, B), lane);
-    }
-  }
-  __syncthreads();
-}
-
-__device__ __forceinline__ unsigned fuse_hash(int row) { return ((unsigned)row * 2654435761u) >> 21; }  // 11 bits
-
-// `row` joins the table if it is new (appended to the dense list then)
-__device__ __forceinline__ void fuse_insert(int row, int* s_key, int* s_idx, int* s_list, int* s_cnt) {
-  unsigned h = fuse_hash(row);
-  for (;;) {
-    const int k = s_key[h];
-    if (k == row) return;
-    if (k == -1) {
-      const int old = atomicCAS(&s_key[h], -1, row);
-      if (old == -1) {
-        const int i = atomicAdd(s_cnt, 1);
-        if (i < FUSE_MAX_CAND) {  // (always: G * P <= 1024 slots are inserted)
-          s_list[i] = row;
-          s_idx[h] = i;
-        }
-        return;
-      }
-      if (old == row) return;
-    }
-    h = (h + 1) & (FUSE_HASH - 1);
-  }
-}
-
-// the place of `row` in the dense list (after the barrier that ends the inserts); -1: not in the table
-__device__ __forceinline__ int fuse_find(int row, const int* s_key, const int* s_idx) {
-  unsigned h = fuse_hash(row);
-  for (int probes = 0; probes < FUSE_HASH; ++probes) {
-    const int k = s_key[h];
-    if (k == row) return s_idx[h];
-    if (k == -1) return -1;
-    h = (h + 1) & (FUSE_HASH - 1);
-  }
-  return -1;
-}
 
 // lzk_dot16_part's order with one accumulator per staged query: this lane's
 // share of <q_j, x> for j < G and of |x|^2; the row is loaded once.
@@ -241,7 +144,9 @@ __global__ __launch_bounds__(FUSE_NT) void fuse_select_kernel(
   // ---- (1) the union: the table and the dense list
   for (int t = tid; t < G * P; t += FUSE_NT) {
     const long r = pools[base * P + t];
-    if (r >= 0 && r < n) fuse_insert((int)r, s_key, s_idx, s_list, &s_cnt);
+    if (r >= 0 && r < n)  // (the list never fills: G * P <= 1024 slots are inserted)
+      lzk_rowset_insert<FUSE_HASH, FUSE_MAX_CAND>((int)r, s_key, s_list, &s_cnt,
+                                                  [&](unsigned h, int i) { s_idx[h] = i; });
   }
   __syncthreads();
   const int cnt = min(s_cnt, FUSE_MAX_CAND);
@@ -254,23 +159,14 @@ __global__ __launch_bounds__(FUSE_NT) void fuse_select_kernel(
       const long r = pj[s];
       if (r < 0 || r >= n) continue;
       ++seen;
-      const int i = fuse_find((int)r, s_key, s_idx);
+      const int i = lzk_rowset_find<FUSE_HASH>((int)r, s_key, s_idx);  // its place in the dense list
       if (i >= 0 && i < FUSE_MAX_CAND && s_rank[i * FUSE_MAX_Q + tid] == 0) s_rank[i * FUSE_MAX_Q + tid] = (unsigned char)seen;
     }
   }
   // |q_j| (mean): group j sums query j's shares in lzk_dot16_part's order
   if (mode == 1 && grp < G) {
-    const float* q = s_q + (long)grp * Dq;
-    float qq = 0.f;
-    if (vec) {
-      for (int d4 = part; d4 < (D >> 2); d4 += 16) {
-        const float4 v = *reinterpret_cast<const float4*>(q + 4 * d4);
-        qq = fmaf(v.x, v.x, qq); qq = fmaf(v.y, v.y, qq); qq = fmaf(v.z, v.z, qq); qq = fmaf(v.w, v.w, qq);
-      }
-    } else {
-      for (int d = part; d < D; d += 16) qq = fmaf(q[d], q[d], qq);
-    }
-    qq = lzk_fold16(qq);  // (a group of 16 lanes is whole or absent: grp is uniform over it)
+    // (a group of 16 lanes is whole or absent: grp is uniform over it)
+    const float qq = lzk_fold16(lzk_sq16_part(s_q + (long)grp * Dq, D, vec, part));
     if (part == 0) s_qn[grp] = sqrtf(qq);
   }
   __syncthreads();
@@ -315,14 +211,14 @@ __global__ __launch_bounds__(FUSE_NT) void fuse_select_kernel(
   // ---- (4) the k best by (score, row)
   const int nb = cnt > 0 ? (cnt + 63) >> 6 : 1;
   for (int i = tid; i < 64 * nb; i += FUSE_NT) s_keys[i] = i < cnt ? wide_key(s_score[i], s_list[i]) : 0ull;
-  topk64_rounds(s_keys, nb);
+  topk64_rounds(s_keys, 0, nb);
   if (tid < k) {
     float v;
     int r;
     wide_unkey(s_keys[tid], v, r);
     int sup = 0;
     if (r >= 0) {
-      const int i = fuse_find(r, s_key, s_idx);
+      const int i = lzk_rowset_find<FUSE_HASH>(r, s_key, s_idx);
       if (i >= 0 && i < FUSE_MAX_CAND)
         for (int j = 0; j < G; ++j) sup += s_rank[i * FUSE_MAX_Q + j] != 0;
     }

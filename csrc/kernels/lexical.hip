@@ -29,7 +29,7 @@
 // slot, the set built from the table when the block starts; with at most 256
 // terms set about 3 % of the other slots pass) and finds each remaining term
 // by a lower-bound search of 8 dependent steps. A match with s > 0 is pushed as a
-// 64-bit (score, row) key -- widek.hip's scheme -- into the query's LDS buffer
+// 64-bit (score, row) key -- lzk_topk64.h's -- into the query's LDS buffer
 // under an LDS atomic counter. Before a step that could overflow a buffer (more than
 // LX_FLUSH entries held, 256 more possible) the block reduces it to its best
 // 64 by the bitonic tournament, takes the 64th as the query's threshold -- a
@@ -46,13 +46,12 @@
 // lex_row_scores; the `k` best by (blend descending, row ascending) come back,
 // (-inf, -1) once the candidates run out.
 //
-// The key and tournament helpers are this file's own copy of widek.hip's.
+// The key and the tournament are lzk_topk64.h's.
 #include "lzk_common.h"
 #include "lzk_dot16.h"
+#include "lzk_topk64.h"
 
 namespace {
-
-typedef unsigned long long u64;
 
 constexpr int LX_NT = 256;
 constexpr int LX_TQ = 8;                   // queries per tile
@@ -68,67 +67,6 @@ constexpr size_t LX_MAX_LDS = 64 * 1024;
 struct LexParams {
   double k1, kp1, omb, b, avgdl;  // k1, k1 + 1, 1 - b, b, avgdl
 };
-
-__device__ __forceinline__ u64 wide_key(float s, int row) {
-  if (!(s == s)) s = LZK_NEG_INF;
-  s += 0.0f;  // -0 -> +0: the order treats them as equal
-  const unsigned u = __float_as_uint(s);
-  const unsigned m = (u >> 31) ? ~u : (u | 0x80000000u);
-  return ((u64)m << 32) | (u64)(0xffffffffu - (unsigned)row);
-}
-
-__device__ __forceinline__ void wide_unkey(u64 key, float& s, int& row) {
-  const unsigned m = (unsigned)(key >> 32);
-  const unsigned u = (m >> 31) ? (m & 0x7fffffffu) : ~m;
-  s = __uint_as_float(u);
-  row = (int)(0xffffffffu - (unsigned)(key & 0xffffffffu));
-  if (m == 0u || s == LZK_NEG_INF) { s = LZK_NEG_INF; row = -1; }
-}
-
-__device__ __forceinline__ u64 kmax(u64 a, u64 b) { return a > b ? a : b; }
-__device__ __forceinline__ u64 kmin(u64 a, u64 b) { return a < b ? a : b; }
-
-// 64 keys, one per lane -> descending by lane.
-__device__ __forceinline__ u64 wave_sort_desc(u64 v, int lane) {
-#pragma unroll
-  for (int k = 2; k <= 64; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const u64 o = __shfl_xor(v, j, 64);
-      const bool low = (lane & j) == 0, desc = (lane & k) == 0;
-      v = (low == desc) ? kmax(v, o) : kmin(v, o);
-    }
-  }
-  return v;
-}
-
-// A bitonic sequence of 64 keys -> descending by lane.
-__device__ __forceinline__ u64 wave_merge_desc(u64 v, int lane) {
-#pragma unroll
-  for (int j = 32; j > 0; j >>= 1) {
-    const u64 o = __shfl_xor(v, j, 64);
-    v = (lane & j) == 0 ? kmax(v, o) : kmin(v, o);
-  }
-  return v;
-}
-
-// keys[0 .. 64 nb): blocks b0 .. nb - 1 are unsorted, blocks below b0 already
-// descending. On return block 0 holds the 64 best of all nb blocks,
-// descending. Every thread of the block calls it (nb, b0 block-uniform).
-__device__ __forceinline__ void topk64_rounds(u64* keys, int b0, int nb) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  __syncthreads();
-  for (int b = b0 + wave; b < nb; b += nw) keys[64 * b + lane] = wave_sort_desc(keys[64 * b + lane], lane);
-  for (int s = 1; s < nb; s <<= 1) {
-    __syncthreads();
-    for (int a = wave * 2 * s; a + s < nb; a += nw * 2 * s) {
-      const u64 A = keys[64 * a + lane];
-      const u64 B = keys[64 * (a + s) + 63 - lane];
-      keys[64 * a + lane] = wave_merge_desc(kmax(A, B), lane);
-    }
-  }
-  __syncthreads();
-}
 
 // s(., r) before the rounding to fp32, for the NQ queries of a term table:
 // tab[TN] sorted ascending (0xffffffff padded), tw[TN][NQ] the weight of each
@@ -317,19 +255,7 @@ __global__ __launch_bounds__(LX_NT) void lex_fuse_kernel(const float* __restrict
   __syncthreads();
 
   // |q|: every group sums the same shares in the same order
-  float qn;
-  {
-    float qq = 0.f;
-    if (vec) {
-      for (int d4 = part; d4 < (D >> 2); d4 += 16) {
-        const float4 v = *reinterpret_cast<const float4*>(s_q + 4 * d4);
-        qq = fmaf(v.x, v.x, qq); qq = fmaf(v.y, v.y, qq); qq = fmaf(v.z, v.z, qq); qq = fmaf(v.w, v.w, qq);
-      }
-    } else {
-      for (int d = part; d < D; d += 16) qq = fmaf(s_q[d], s_q[d], qq);
-    }
-    qn = sqrtf(lzk_fold16(qq));
-  }
+  const float qn = sqrtf(lzk_fold16(lzk_sq16_part(s_q, D, vec, part)));
   const float dn = den[m];
 
   for (int f0 = 0; f0 < LX_MAX_C; f0 += LX_NT / 16) {  // (block-uniform trip count: the folds run with whole waves)

@@ -30,7 +30,7 @@
 // rows get bit-identical dots, norms and objectives, so the row decides
 // between them. A launch takes one path for every dot it computes.
 #include "lzk_common.h"
-#include "lzk_dot16.h"  // lzk_dot16_part, lzk_fold16, lzk_cos: the layout stated above
+#include "lzk_dot16.h"  // lzk_dot16_part, lzk_sq16_part, lzk_fold16, lzk_cos: the layout stated above
 
 namespace {
 
@@ -65,19 +65,7 @@ __global__ __launch_bounds__(MMR_NT) void mmr_select_kernel(
   __syncthreads();
 
   // ---- |q|: every group sums the same shares in the same order
-  float qn;
-  {
-    float qq = 0.f;
-    if (vec) {
-      for (int d4 = part; d4 < (D >> 2); d4 += 16) {
-        const float4 v = *reinterpret_cast<const float4*>(s_q + 4 * d4);
-        qq = fmaf(v.x, v.x, qq); qq = fmaf(v.y, v.y, qq); qq = fmaf(v.z, v.z, qq); qq = fmaf(v.w, v.w, qq);
-      }
-    } else {
-      for (int d = part; d < D; d += 16) qq = fmaf(s_q[d], s_q[d], qq);
-    }
-    qn = sqrtf(lzk_fold16(qq));
-  }
+  const float qn = sqrtf(lzk_fold16(lzk_sq16_part(s_q, D, vec, part)));
 
   // ---- relevance and norms of the owned slots
   for (int f0 = 0; f0 < F; f0 += MMR_NT / 16) {  // (block-uniform trip count: the folds run with whole waves)

@@ -34,7 +34,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from .mmr_ops import MMR_SUM_DEPTH as EXPAND_SUM_DEPTH  # expand.hip uses mmr.hip's dot layout (csrc/include/lzk_dot16.h)
+from ._dot16 import cos_or_zero
+from ._dot16 import sum_depth as EXPAND_SUM_DEPTH  # expand.hip uses mmr.hip's dot layout (csrc/include/lzk_dot16.h)
 
 NEG_INF = float("-inf")
 NODE = 1  # (engine.tenant_graph NODE: the kind of a graph node)
@@ -94,11 +95,6 @@ def _check(X, Q, seeds, csr, w, kind, sup, bias, spec, limit):
     return sp, Q, seeds, M, S
 
 
-def _cos(dot, na, nb):
-    ok = (na > 0) & (nb > 0)
-    return torch.where(ok, dot / torch.where(ok, na * nb, torch.ones_like(dot)), torch.zeros_like(dot))
-
-
 def expand_select_ref(X, Q, seeds, csr, w, kind, sup, bias, spec, limit):
     """Torch formulation of :func:`expand_select` (any device), fp32
     throughout. Per query the candidate table is a sorted row list; a hop
@@ -126,7 +122,7 @@ def expand_select_ref(X, Q, seeds, csr, w, kind, sup, bias, spec, limit):
 
     def cos_rows(m, rows):
         x = X[rows].to(torch.float32)
-        return _cos(x @ Qf[m], x.norm(dim=1), qn[m].expand(rows.numel()))
+        return cos_or_zero(x @ Qf[m], x.norm(dim=1), qn[m].expand(rows.numel()))
 
     for m in range(M):
         s = seeds[m].to(dev).long()

@@ -44,7 +44,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .mmr_ops import MMR_SUM_DEPTH as FUSE_SUM_DEPTH  # fuse.hip uses mmr.hip's dot layout (csrc/include/lzk_dot16.h)
+from ._dot16 import cos_or_zero
+from ._dot16 import sum_depth as FUSE_SUM_DEPTH  # fuse.hip uses mmr.hip's dot layout (csrc/include/lzk_dot16.h)
 from ..core.fuse import MAX_FUSE_Q, MAX_LIMIT, MAX_POOL, QueryFusion
 
 NEG_INF = float("-inf")
@@ -133,11 +134,6 @@ def _check(X, Q, offsets, pools, k, fusion, weights):
     return fu, Q, sizes, w32, M, P, k
 
 
-def _cos(dot, na, nb):
-    ok = (na > 0) & (nb > 0)
-    return torch.where(ok, dot / torch.where(ok, na * nb, torch.ones_like(dot)), torch.zeros_like(dot))
-
-
 def fuse_select_ref(X, Q, offsets, pools, k, fusion="rrf", weights=None, n: Optional[int] = None):
     """Torch formulation of :func:`fuse_select` (any device). Per group the
     union is the sorted unique rows, the first occurrences come from an
@@ -184,7 +180,7 @@ def fuse_select_ref(X, Q, offsets, pools, k, fusion="rrf", weights=None, n: Opti
             score = torch.zeros(C, dtype=torch.float32, device=dev)
             for j in range(G):
                 q = Q[a + j].to(dev, torch.float32)
-                score = score + w[a + j] * _cos(x @ q, xn, q.norm().expand(C))
+                score = score + w[a + j] * cos_or_zero(x @ q, xn, q.norm().expand(C))
         o = torch.sort(score, descending=True, stable=True).indices[:k]  # (rows ascend: ties to the lower row)
         c = o.numel()
         orow[g, :c], oscore[g, :c], osup[g, :c] = U[o], score[o], (R[o] > 0).sum(1).int()

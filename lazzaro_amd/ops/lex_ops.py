@@ -52,6 +52,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._dot16 import sum_depth as LEX_SUM_DEPTH  # lex_fuse uses mmr.hip's dot layout (csrc/include/lzk_dot16.h)
 
 NEG_INF = float("-inf")
 T_MAX = 32      # lexical.hip LX_T
@@ -59,12 +60,6 @@ TILE_Q = 8      # lexical.hip LX_TQ
 MAX_K = 64
 SLOT_CHOICES = (8, 16, 32)
 PAD_TERM = 0xFFFFFFFF
-
-
-def LEX_SUM_DEPTH(D: int) -> int:
-    """fp32 roundings one dot product of lex_fuse passes through (lzk_dot16.h:
-    a lane's fma chain over its share of the dimensions, then 4 shuffle adds)."""
-    return 4 * -(-int(D) // 64) + 4
 
 
 def lex_tol(D: int) -> float:

@@ -20,17 +20,11 @@ from typing import Tuple
 import torch
 
 from . import _lib
+from ._dot16 import cos_or_zero
+from ._dot16 import sum_depth as MMR_SUM_DEPTH  # L(D) of mmr.hip's 'Summation order' (csrc/include/lzk_dot16.h)
 
 NEG_INF = float("-inf")
 MAX_FETCH_K = 64  # mmr.hip MMR_MAX_F: one pool slot per lane of the selecting wave
-
-
-def MMR_SUM_DEPTH(D: int) -> int:
-    """fp32 roundings one dot product of the kernel passes through (mmr.hip,
-    'Summation order'): a lane's chain of fmas over its share of the
-    dimensions -- 4 per float4 it owns, ceil(D / 4 / 16) of them at most; the
-    scalar path's ceil(D / 16) is never longer -- and the 4 shuffle adds."""
-    return 4 * -(-int(D) // 64) + 4
 
 
 def mmr_tol(D: int) -> float:
@@ -81,11 +75,6 @@ def _check(X, Q, cand, k, diversity):
     return Q, cand, M, F
 
 
-def _cos(dot, na, nb):
-    ok = (na > 0) & (nb > 0)
-    return torch.where(ok, dot / torch.where(ok, na * nb, torch.ones_like(dot)), torch.zeros_like(dot))
-
-
 def mmr_select_ref(X: torch.Tensor, Q: torch.Tensor, cand: torch.Tensor, k: int, diversity: float,
                    chunk: int = 128) -> Tuple[torch.Tensor, torch.Tensor]:
     """Torch formulation of :func:`mmr_select` (any device), fp32 throughout:
@@ -110,9 +99,9 @@ def mmr_select_ref(X: torch.Tensor, Q: torch.Tensor, cand: torch.Tensor, k: int,
         key = torch.where(alive, c, torch.full_like(c, BIG))
         Xc = X[c.clamp(0, n - 1)].to(torch.float32)             # [mm, F, D]
         nrm = Xc.norm(dim=2)
-        rel = _cos(torch.einsum("md,mfd->mf", q, Xc), q.norm(dim=1)[:, None].expand(-1, F), nrm)
-        sim = _cos(torch.bmm(Xc, Xc.transpose(1, 2)), nrm[:, :, None].expand(-1, -1, F),
-                   nrm[:, None, :].expand(-1, F, -1))
+        rel = cos_or_zero(torch.einsum("md,mfd->mf", q, Xc), q.norm(dim=1)[:, None].expand(-1, F), nrm)
+        sim = cos_or_zero(torch.bmm(Xc, Xc.transpose(1, 2)), nrm[:, :, None].expand(-1, -1, F),
+                          nrm[:, None, :].expand(-1, F, -1))
         mx = torch.full((mm, F), NEG_INF, dtype=torch.float32, device=dev)
         for t in range(k):
             red = torch.zeros_like(mx) if t == 0 else mx

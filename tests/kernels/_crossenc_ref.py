@@ -188,7 +188,9 @@ def token_case(M: int, P: int, n: int, L: int, vocab: int, seed: int = 0, max_po
 
 # (H, M, P, k, what): the head's cases -- ties from duplicated pooler rows, empty slots, limit = 1, limit = P, P = 64
 HEAD_CASES = [(128, 3, 5, 1, "ties"), (128, 3, 5, 5, "ties"), (384, 4, 16, 7, "ties"), (1024, 2, 64, 64, "ties"),
-              (384, 2, 64, 16, "plain")]
+              (384, 2, 64, 16, "plain"),
+              # the shared wave sort (lzk_topk64.h) with a nearly empty and a full 64-entry block, a prefix of 4 returned
+              (128, 3, 5, 4, "ties"), (1024, 2, 64, 4, "ties")]
 
 
 def head_case(H: int, M: int, P: int, what: str, seed: int = 0):

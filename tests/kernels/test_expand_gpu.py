@@ -300,6 +300,22 @@ def test_empty_duplicate_and_out_of_range_seeds():
     assert got[3][0] == 0 and (got[0][0] == -1).all() and np.isneginf(got[1][0]).all()
 
 
+def test_rows_that_collide_in_the_table_hash_are_separate_entries():
+    """Two pairs of rows whose first probe is the same slot of the row table
+    (Knuth's multiplier, the top 11 bits: csrc/include/lzk_rowset.h). (a, a2):
+    a seed, listed twice, and the target it reaches in the hop. (b, b2): two
+    seeds inserted side by side. Each row is one entry."""
+    c = _case(20)
+    ok = np.flatnonzero((c["kind"] == 1) & (c["sup"] == 0) & np.isfinite(c["bias"]))
+    h = ((ok.astype(np.uint64) * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)) >> np.uint64(21)
+    full = np.flatnonzero(np.bincount(h.astype(np.int64), minlength=2048) >= 2)
+    assert full.size >= 2, "no two pairs of rows share a slot: the case does not test the probing"
+    (a, a2), (b, b2) = (ok[h == s][:2].tolist() for s in full[:2])
+    g = _graph(c, [(a, a2, 0.9), (b, a2, 0.8)], [a, b, b2, a])
+    rows, scores, via, ncand = _cands(g, GraphExpand(hops=1, fanout=2, seed_k=4), [a, a2, b, b2])
+    assert (rows[0][4:] == -1).all()
+
+
 def test_a_graph_without_edges_returns_the_seeds_by_cosine():
     c = _graph(_case(20, M=32, n=512, seed=3), [], [0], M=32)   # (empty adj, eid and w: null pointers on the device)
     c["seeds"] = _case(20, M=32, n=512, seed=3)["seeds"]

@@ -100,6 +100,48 @@ def test_rrf_one_slot_pools_and_the_full_table():
         assert out[3].tolist() == [1024, 1024]
 
 
+# ---- the shared tournament and row table (csrc/include/lzk_topk64.h, lzk_rowset.h) at their smallest shapes
+@pytest.mark.parametrize("mode", ["rrf", "mean"])
+def test_three_blocks_one_block_ties_and_colliding_rows(mode):
+    """n = 1,024 (the first 256 rows collide nowhere in the hash), D = 64, k =
+    64. Group 0: three disjoint pools of 64, so 192
+    candidates in three 64-entry blocks -- the third has no partner in the
+    tournament's first round. Group 1: one pool of 16 with a row listed twice:
+    15 candidates in a single block. Rows a < b open pools 0 and 1 and collide
+    in the table's 11-bit hash; rows u < v hold one embedding, the best for
+    every sub-query, so ``mean`` ties them bit for bit; under ``rrf`` the
+    three pools tie rank by rank. Ties go to the lower row."""
+    n, D, k = 1024, 64, 64
+    rng = np.random.default_rng(11)
+    h = ((np.arange(n, dtype=np.uint64) * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)) >> np.uint64(21)
+    a, b = next((int(np.flatnonzero(h[:j] == h[j])[0]), j) for j in range(n) if (h[:j] == h[j]).any())
+    u, v = [r for r in range(n) if r not in (a, b)][:2]
+    rest = rng.permutation([r for r in range(n) if r not in (a, b, u, v)])
+    p3 = np.concatenate([[a, u], rest[:62], [b, v], rest[62:124], rest[124:188]]).reshape(3, 64).astype(np.int64)
+    p1 = np.full((1, 64), -1, dtype=np.int64)
+    p1[0, :16] = np.concatenate([[b, a], rest[188:201], [b]])
+    pools = np.concatenate([p3, p1])
+    off = [0, 3, 4]
+    base = rng.standard_normal(D)
+    X = rng.standard_normal((n, D))
+    X[u] = X[v] = 3.0 * base
+    X = (X / np.linalg.norm(X, axis=1, keepdims=True)).astype(np.float32)
+    Q = (base + 0.3 * rng.standard_normal((4, D))).astype(np.float32)
+    assert np.unique(p3).size == 192 and np.array_equal(X[u], X[v])
+    if mode == "rrf":
+        out = _np(fuse_select(None, None, off, _dev(pools), k, "rrf", n=n))
+        R.check_rrf(R.fuse64(off, pools, n, "rrf", 60.0), k, *out)
+        assert out[0][0, :6].tolist() == sorted([a, b, int(p3[2, 0])]) + sorted([u, v, int(p3[2, 1])])
+    else:
+        out = _np(fuse_select(_dev(X), _dev(Q), off, _dev(pools), k, "mean"))
+        R.check_mean(R.fuse64(off, pools, n, "mean", X=X, Q=Q), k, *out, D)
+        assert out[0][0, :2].tolist() == [u, v] and out[1][0, 0].view(np.uint32) == out[1][0, 1].view(np.uint32)
+    rows = out[0]
+    assert out[3].tolist() == [192, 15] and (rows[1, 15:] == -1).all()
+    # colliding rows: one entry each (group 1 returns all it has; group 0 ranks both first under rrf)
+    assert all((rows[g] == r).sum() == 1 for g in ((0, 1) if mode == "rrf" else (1,)) for r in (a, b))
+
+
 # ---- mean: the two rules
 @pytest.mark.parametrize("D,P,G,k,NG", R.FULL_ORDER_CASES, ids=_ids5)
 def test_mean_holds_the_two_rules(D, P, G, k, NG):

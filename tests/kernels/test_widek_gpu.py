@@ -94,6 +94,30 @@ def test_select_wide_walks_lists_past_its_lds_in_pieces_gpu():
     assert np.array_equal(r, e_r) and np.array_equal(s.astype(np.float64), e_s) and np.array_equal(ovf, e_o)
 
 
+def test_select_wide_smallest_tournaments_nan_and_negative_zero_gpu():
+    """The shared tournament (csrc/include/lzk_topk64.h) called with a running
+    best in block 0: one staged block (cap = 64), three with the last partly
+    filled (130 of cap = 192), and the shortest list that takes two pieces
+    (16,384 + 100). A nan selects as -inf does; -0 and +0 are one score, so
+    the row decides among them."""
+    rng = np.random.default_rng(12)
+    nq, kout = 2, 64
+    for cap, c in ((64, 64), (192, 130), (16384 + 100, 16384 + 100)):
+        _, cs, ci, _ = _lists(rng, nq, cap, kout)
+        cs = -np.abs(cs)  # (the zeros, every drawn one a -0, are the plateau at the top)
+        cnt = np.full(nq, c, dtype=np.int32)
+        for at, sc, row in ((3, np.nan, 1), (7, -0.0, 50), (9, 0.0, 20), (11, -0.0, 35), (c - 2, -0.0, 10),
+                            (c - 1, np.nan, 2)):
+            cs[:, at], ci[:, at] = sc, row
+        e_s, e_r, e_o = R.select_ref(cnt, np.where(np.isnan(cs), F32(NEG_INF), cs), ci, cap, kout)
+        s, r, ovf = _select(cnt, cs, ci, cap, kout)
+        assert np.array_equal(r, e_r), (cap, r[0], e_r[0])
+        assert np.array_equal(s.astype(np.float64), e_s) and np.array_equal(ovf, e_o)
+        assert not np.isnan(s).any()
+        for q in range(nq):  # (the case means what it says: the four zeros are among the 64)
+            assert {10, 20, 35, 50} <= {int(x) for x, v in zip(r[q], s[q]) if v == 0.0}, (cap, r[q])
+
+
 def test_select_wide_as_a_masked_merge_gpu():
     """cnt null (every list full), q_active given: inactive queries' outputs
     stay as they were; nothing at all is written when none is active."""
